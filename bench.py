@@ -7,7 +7,11 @@ Multi-GPU: one process per GPU, each integrates its own object (objects are inde
 reconstruct_rgbd_filter.py:154-155) => weak scaling, no data-path collective; barrier + max-over-ranks
 timing.  Prints ONE JSON line on rank 0.
 
-Also reported:
+A plain run (`bench.py --gpus N --steps K --warmup W`) renders the headline scan, warms up, times the K steps, writes
+the last step's volume with --dump-outputs DIR, and prints the result line (metric, value, unit, ms_per_step, ...);
+the legs below are None in it.
+
+Also reported with --full (every leg keeps its own switch, e.g. --cpu-frames 0 or --sustain 0):
   roofline     — dominant kernel (k_batch_integrate<true>, float64 colour): the measured HBM bytes per launch from
                  rocprofv3 PMC counters (profiles/pmc_traffic.json, used only when its source hash and workload match
                  this build) over its mean device time measured with HIP events on the launch stream (`frac`, physical,
@@ -47,6 +51,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg after the timed steps (sustained, roofline, colour-32 headline, "
+                         "configs[0] / [2] / [3] / [4], spatial sharding, CPU baselines); without it only the headline "
+                         "is set up and timed and those legs are null in the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the volume the last step left as DIR/<name>.npy (rank r > 0: "
+                         "DIR/rank<r>/): every unit's key and per-unit sums, and the voxels of a fixed seeded sample "
+                         "of units")
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--voxel", type=float, default=0.005)
     ap.add_argument("--sdf-trunc", type=float, default=0.04)
@@ -152,16 +164,17 @@ def main():
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    full = args.full  # a plain run sets up and times the headline only; every other leg needs --full
     # configs[3] scans are rendered before this process touches the GPU (the render pool forks workers)
     synth0 = importlib.import_module(PKG + ".synth")
     obj_ids = list(range(args.objects))[(args.objects * rank) // world:(args.objects * (rank + 1)) // world]
-    obj_scans = _render_objects(synth0, obj_ids, args.object_frames) if args.objects > 0 else None
+    obj_scans = _render_objects(synth0, obj_ids, args.object_frames) if (full and args.objects > 0) else None
     # every scan is rendered by forked workers before this process touches the GPU
     head_scan = synth0.make_sequence_parallel(synth0.Scene(seed=rank), n_frames=args.frames,
                                               intr=synth0.REF_INTRINSICS_640)
     filt_frames = synth0.make_sequence_parallel(synth0.Scene(seed=rank), n_frames=args.filter_frames,
                                                 intr=synth0.REF_INTRINSICS_1280) \
-        if (args.filter_frames > 0 and rank == 0) else None
+        if (full and args.filter_frames > 0 and rank == 0) else None
     # OT_BENCH_BACKEND=gloo + OT_BENCH_SHARE_GPU=1 rehearse the N-rank path on a one-GPU box (every rank on
     # device 0, collectives through host memory); the driver's runs use RCCL ("nccl"), one GPU per rank.
     backend = os.environ.get("OT_BENCH_BACKEND", "nccl")
@@ -182,7 +195,8 @@ def main():
     L = importlib.import_module(PKG + "._lib")
     lib = L.load()
     # the concurrent legs' worker streams, created once and first (distinct hardware queues; streams.py)
-    importlib.import_module(PKG + ".streams").worker_streams(max(args.filter_streams, args.object_streams, 1))
+    if full:
+        importlib.import_module(PKG + ".streams").worker_streams(max(args.filter_streams, args.object_streams, 1))
 
     # ---- synthetic object scan for this rank (same geometry, rank-seeded noise) ----
     intr_t = synth.REF_INTRINSICS_640
@@ -234,9 +248,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:  # the volume as the last timed step left it
+        dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     L, torch, vol, stream)
+
     # ---- sustained: the same step back to back for >= args.sustain seconds (corroborates value over a long window) ----
     sustained = None
-    if args.sustain > 0:
+    if full and args.sustain > 0:
         n_s, t_s = 0, time.perf_counter()
         while time.perf_counter() - t_s < args.sustain:
             step()
@@ -253,6 +271,114 @@ def main():
     n_units = C.c_int64(0)
     L.call("ot_tsdf_num_units", vol, C.byref(n_units), stream)
 
+    frames_total = world * args.frames * args.steps
+    value = frames_total / elapsed
+    ms_per_step = elapsed * 1e3 / args.steps
+    roofline, frontend_ms, kernel_ms_avg = headline_roofline(args, L, vol, step, W, H, upd.value) if full \
+        else (None, 0.0, 0.0)
+
+    # configs[2] stream set up (uploaded, handles + worker threads warmed) before the other legs allocate
+    fstream = FilterStream(args, L, synth, torch, filt_frames) if filt_frames is not None else None
+    color32 = headline_color32(args, L, lib, torch, dist, world, d_depth, d_color, ext, intr, stream, upd.value) \
+        if (full and args.color32 and args.color_bits == 64) else None
+
+    # leg order (DESIGN.md §5): OT_BENCH_ORDER may repeat legs and insert "sleep" (5 s idle) for diagnosis; the
+    # reported filtered / objects objects are the first run of each, later filtered runs go to filtered_repeat_ms
+    order = os.environ.get("OT_BENCH_ORDER", "filtered,objects").split(",")
+    filt = objects = None
+    filt_repeat = []
+    for leg in order:
+        if leg == "filtered" and fstream is not None:
+            r = fstream.run()
+            if filt is None:
+                filt = r
+            else:
+                filt_repeat.append(r["ms_per_frame"])
+        if leg == "objects" and obj_scans is not None:
+            r = objects_pipeline(args, L, lib, synth, torch, dist, rank, world, obj_ids, obj_scans)
+            objects = objects or r
+        if leg == "sleep" and full:
+            time.sleep(5.0)
+    if fstream is not None:
+        fstream.close()
+    if filt is not None and filt_repeat:
+        filt["filtered_repeat_ms"] = filt_repeat
+    hybrid = hybrid_fusion(args, L, synth, torch, dist, rank, world) if (full and args.hybrid_objects > 0) else None
+
+    spatial = spatial_shard(args, L, lib, synth, torch, dist, rank, world, n_units.value) \
+        if (full and world > 1 and args.spatial) else None
+    shard_steps = shard_rank_steps(args, L, lib, torch, d_depth, d_color, ext, intr, stream, ms_per_step) \
+        if (full and world == 1 and args.shard_steps > 0) else None
+
+    cpu = None
+    if full and rank == 0 and args.cpu_frames > 0:
+        cpu = cpu_baseline(depth, color, ext, intr_t, args)
+    single = single_frame(L, synth, torch, depth, color, ext, intr_t) \
+        if (full and rank == 0 and args.cpu_frames > 0) else None
+
+    out = {"metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32 tsdf/weight + f64 colour" if args.color_bits == 64 else "f32 (colour state f32)",
+           "data": "synthetic", "full": full,
+           "config": {"workload": "configs[1]: 256-frame 640x480 RGB-D TSDF integration, 5 mm voxel, "
+                                  "sdf_trunc 0.04, one object scan per GPU (synthetic box-on-floor ring scan), "
+                                  f"colour precision {args.color_bits}" +
+                                  (" (Open3D's float64 TSDFVoxel::color_, exact division: bit-exact colours)"
+                                   if args.color_bits == 64 else " (float32 colour state, |rel| <= 1e-4)"),
+                      "color_precision": args.color_bits,
+                      "frames_per_step": args.frames, "width": W, "height": H, "voxel_length": args.voxel,
+                      "sdf_trunc": args.sdf_trunc, "volume_units": n_units.value,
+                      "unit_integrations_per_step": unit_int.value, "parallelism": f"objects{world}"},
+           "roofline": roofline, "cpu_baseline": cpu, "sustained": sustained, "color32": color32,
+           "spatial_amdahl": spatial_amdahl(frontend_ms, kernel_ms_avg, shard_steps),
+           "filtered": filt, "objects": objects,
+           "hybrid_map": hybrid, "single_frame": single, "spatial": spatial, "source_hash": L.source_hash()}
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    L.call("ot_tsdf_destroy", vol)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+DUMP_SAMPLE_UNITS = 256  # 256 x 4096 voxels x (4 + 4 + 24) B = 32 MiB of voxel rows
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, L, torch, vol, stream):
+    """--dump-outputs: what a caller reads back from the volume after a step (ot_tsdf_export_units +
+    ot_tsdf_export_color64: units sorted by key, voxels in Open3D IndexOf order), as <out_dir>/<name>.npy:
+      unit_keys     (U, 3) float64   every unit's key (int32 values);
+      unit_sums     (U, 5) float64   per unit the float64 sums of tsdf, weight and the three colour channels;
+      sample_units  (S,)   float64   the rows of a fixed seeded sample of S = min(U, 256) units, ascending;
+      tsdf, weight  (S, 4096) float32 and color (S, 4096, 3) float64: the sampled units' voxels.
+    The whole volume is U x 128 KiB (0.7 GiB at the default size), hence the sample; the sums cover every voxel."""
+    n = C.c_int64(0)
+    L.call("ot_tsdf_num_units", vol, C.byref(n), stream)
+    n = n.value
+    keys = torch.empty((n, 3), dtype=torch.int32, device="cuda")
+    tsdf = torch.empty((n, 4096), dtype=torch.float32, device="cuda")
+    weight = torch.empty((n, 4096), dtype=torch.float32, device="cuda")
+    color = torch.empty((n, 4096, 3), dtype=torch.float64, device="cuda")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    L.call("ot_tsdf_export_units", vol, n, ptr(keys), ptr(tsdf), ptr(weight), None, stream)
+    L.call("ot_tsdf_export_color64", vol, n, ptr(color), stream)
+    sums = torch.cat([tsdf.sum(1, dtype=torch.float64)[:, None], weight.sum(1, dtype=torch.float64)[:, None],
+                      color.sum(1)], 1)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE_UNITS), replace=False)) \
+        if n > 0 else np.zeros(0, np.int64)
+    rows = torch.from_numpy(pick).cuda()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("unit_keys", keys.cpu().numpy().astype(np.float64)), ("unit_sums", sums.cpu().numpy()),
+                      ("sample_units", pick.astype(np.float64)), ("tsdf", tsdf[rows].cpu().numpy()),
+                      ("weight", weight[rows].cpu().numpy()), ("color", color[rows].cpu().numpy())):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
+def headline_roofline(args, L, vol, step, W, H, updates):
+    """--full: the dominant kernel's roofline from one extra (untimed) step of the headline volume with HIP events
+    around every launch.  Returns (roofline, front-end ms per batch, kernel ms per launch)."""
     # ---- roofline: one extra (untimed) step with HIP events around every dominant-kernel launch ----
     L.call("ot_tsdf_set_profiling", vol, 1)
     step()
@@ -265,13 +391,10 @@ def main():
     sb, sub, sfresh = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     L.call("ot_tsdf_batch_stats", vol, C.byref(sb), C.byref(sub), C.byref(sfresh))
 
-    frames_total = world * args.frames * args.steps
-    value = frames_total / elapsed
-    ms_per_step = elapsed * 1e3 / args.steps
     # 40 B per voxel update = read + write of a 20-B record (f32 tsdf, weight, 3 x f32 colour) whatever
     # the layout -- also at colour precision 64, whose record is 32 B (the figure stays the survey's, so the two
     # precisions' fractions compare the same work)
-    algo_bytes_step = 5.0 * W * H * args.frames + 40.0 * upd.value
+    algo_bytes_step = 5.0 * W * H * args.frames + 40.0 * updates
     per_launch_bytes = algo_bytes_step / max(klaunch.value, 1)
     kernel_ms_avg = kms.value / max(klaunch.value, 1)
     achieved = per_launch_bytes / (kernel_ms_avg * 1e-3) / 1e9 if kernel_ms_avg > 0 else 0.0
@@ -296,14 +419,13 @@ def main():
                 "color_bits": args.color_bits,
                 "kernel_ms_avg": round(kernel_ms_avg, 5), "launches_per_step": klaunch.value,
                 "algorithmic_bytes_per_launch": round(per_launch_bytes),
-                "voxel_updates_per_frame": round(upd.value / args.frames)}
+                "voxel_updates_per_frame": round(updates / args.frames)}
     if hbm_achieved:  # kept under the old names too (round-3/4 records)
         roofline["hbm_achieved"] = roofline["achieved"]
         roofline["hbm_frac"] = roofline["frac"]
         roofline["traffic_level"] = ("L2-miss (fabric) bytes: FETCH_SIZE / WRITE_SIZE count the requests that leave "
-                                     "the XCD's L2, including those the Infinity Cache (MALL) then serves "
-                                     "(MI355X_MICROARCH.md), so the DRAM bytes may be lower and `frac` is an upper "
-                                     "bound on the HBM fraction")
+                                     "the XCD's L2, including those the Infinity Cache (MALL) then serves, so "
+                                     "the DRAM bytes may be lower and `frac` is an upper bound on the HBM fraction")
     # compulsory bytes per launch: the touched units' state read once (units new in the batch
     # start from zero: not read) and written once, plus the batch's staged frames read once (8-B depth / multiplier +
     # 4-B colour per pixel) -- what a kernel that re-fetched nothing would move
@@ -329,69 +451,7 @@ def main():
         roofline["traffic_raw"] = {k: ient.get(k) for k in ("raw_fetch_kib", "raw_write_kib", "fetch_correction",
                                                             "fetch_correction_source", "write_correction")}
 
-    # configs[2] stream set up (uploaded, handles + worker threads warmed) before the other legs allocate
-    fstream = FilterStream(args, L, synth, torch, filt_frames) if (args.filter_frames > 0 and rank == 0) else None
-    color32 = headline_color32(args, L, lib, torch, dist, world, d_depth, d_color, ext, intr, stream, upd.value) \
-        if (args.color32 and args.color_bits == 64) else None
-
-    # leg order (DESIGN.md §5): OT_BENCH_ORDER may repeat legs and insert "sleep" (5 s idle) for diagnosis; the
-    # reported filtered / objects objects are the first run of each, later filtered runs go to filtered_repeat_ms
-    order = os.environ.get("OT_BENCH_ORDER", "filtered,objects").split(",")
-    filt = objects = None
-    filt_repeat = []
-    for leg in order:
-        if leg == "filtered" and fstream is not None:
-            r = fstream.run()
-            if filt is None:
-                filt = r
-            else:
-                filt_repeat.append(r["ms_per_frame"])
-        if leg == "objects" and args.objects > 0:
-            r = objects_pipeline(args, L, lib, synth, torch, dist, rank, world, obj_ids, obj_scans)
-            objects = objects or r
-        if leg == "sleep":
-            time.sleep(5.0)
-    if fstream is not None:
-        fstream.close()
-    if filt is not None and filt_repeat:
-        filt["filtered_repeat_ms"] = filt_repeat
-    hybrid = hybrid_fusion(args, L, synth, torch, dist, rank, world) if args.hybrid_objects > 0 else None
-
-    spatial = spatial_shard(args, L, lib, synth, torch, dist, rank, world, n_units.value) \
-        if (world > 1 and args.spatial) else None
-    shard_steps = shard_rank_steps(args, L, lib, torch, d_depth, d_color, ext, intr, stream, ms_per_step) \
-        if (world == 1 and args.shard_steps > 0) else None
-
-    cpu = None
-    if rank == 0 and args.cpu_frames > 0:
-        cpu = cpu_baseline(depth, color, ext, intr_t, args)
-    single = single_frame(L, synth, torch, depth, color, ext, intr_t) if (rank == 0 and args.cpu_frames > 0) \
-        else None
-
-    out = {"metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None,
-           "dtype": "f32 tsdf/weight + f64 colour" if args.color_bits == 64 else "f32 (colour state f32)",
-           "data": "synthetic",
-           "config": {"workload": "configs[1]: 256-frame 640x480 RGB-D TSDF integration, 5 mm voxel, "
-                                  "sdf_trunc 0.04, one object scan per GPU (synthetic box-on-floor ring scan), "
-                                  f"colour precision {args.color_bits}" +
-                                  (" (Open3D's float64 TSDFVoxel::color_, exact division: bit-exact colours)"
-                                   if args.color_bits == 64 else " (float32 colour state, |rel| <= 1e-4)"),
-                      "color_precision": args.color_bits,
-                      "frames_per_step": args.frames, "width": W, "height": H, "voxel_length": args.voxel,
-                      "sdf_trunc": args.sdf_trunc, "volume_units": n_units.value,
-                      "unit_integrations_per_step": unit_int.value, "parallelism": f"objects{world}"},
-           "roofline": roofline, "cpu_baseline": cpu, "sustained": sustained, "color32": color32,
-           "spatial_amdahl": spatial_amdahl(fms.value / max(fbatches.value, 1), kernel_ms_avg, shard_steps),
-           "filtered": filt, "objects": objects,
-           "hybrid_map": hybrid, "single_frame": single, "spatial": spatial, "source_hash": L.source_hash()}
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    L.call("ot_tsdf_destroy", vol)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    return roofline, fms.value / max(fbatches.value, 1), kernel_ms_avg
 
 
 def headline_color32(args, L, lib, torch, dist, world, d_depth, d_color, ext, intr, stream, updates_c64):

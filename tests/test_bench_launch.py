@@ -28,6 +28,21 @@ def test_resolve_world_table():
         b.resolve_world(1, {"WORLD_SIZE": "2"})
 
 
+def test_plain_run_is_the_default():
+    """--full and --dump-outputs are off unless given; --steps / --warmup are taken as given."""
+    b = _bench()
+    saved = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = b.parse()
+        assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "d"]
+        a = b.parse()
+        assert a.full is True and a.dump_outputs == "d"
+    finally:
+        sys.argv = saved
+
+
 def test_launch_ranks_environment(tmp_path):
     """Each child sees its RANK / LOCAL_RANK, the common WORLD_SIZE and a 127.0.0.1 rendezvous; exit 0 overall."""
     b = _bench()
