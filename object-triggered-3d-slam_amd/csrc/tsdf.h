@@ -152,8 +152,9 @@ struct BatchFrame {
     const uint16_t* depth16;  // raw depth (u16 path) or nullptr
     const float* depthf;      // caller's float depth (float path) or nullptr
     const uint8_t* color;     // caller's RGB8 or nullptr
-    float2* dm;               // packed per-pixel (depth, ray multiplier) staged by k_batch_touch
-    uint32_t* rgba;           // packed per-pixel colour r | g << 8 | b << 16 staged by k_batch_touch
+    uint2* dc;                // staged per-pixel record: .x the float depth's bits, .y the colour r | g << 8 | b << 16
+                              // (0 without colour); 8 B per pixel -- the ray multiplier is the volume's one table
+    uint64_t pad;             // (the struct is copied in 16-B words)
     double pose[12];          // rows 0..2 of inverse(extrinsic) (stride unprojection, float64)
     float E[12];              // rows 0..2 of (float)extrinsic
     float es[3];              // column 2 of (float)extrinsic * voxel_length
@@ -224,15 +225,14 @@ struct ot_tsdf {
     int early_frame = -1;
     unsigned mc_seq = 0;  // the marching-cubes totals' sequence number (words MAIL_SEQ_MC, MAIL_SEQ_MC + 1)
     int batch_pc = ot::C_BATCH_PAIRS;      // pair counter of the next batch (alternates 4, 5)
-    // A batch's staging: per-frame parameters, packed (depth, multiplier) and colour per pixel, and the unit work list.
+    // A batch's staging: per-frame parameters, the packed (depth, colour) record per pixel, and the unit work list.
     // Two sets: with the front end double-buffered (overlap, ot_tsdf_set_frontend_overlap: off by default, measured slower
     // sharded volume, whose integrate is 1/N of the work) batch k+1's staging / touch / units run on the caller's stream
     // while batch k's integrate runs on `istream`; otherwise set 0 only, everything on the caller's stream.
     struct BatchSet {
         ot::BatchFrame* bframes = nullptr;  // device [MAX_BATCH]
-        float2* bdm = nullptr;              // device [batch][h][w] packed (depth, multiplier)
-        uint32_t* brgba = nullptr;          // device [batch][h][w] packed colour
-        int64_t cap = 0;                    // pixels (frames * h * w) the two buffers hold
+        uint2* bdc = nullptr;               // device [batch][h][w] packed (depth, colour) records
+        int64_t cap = 0;                    // pixels (frames * h * w) the buffer holds
         void* work = nullptr;               // UnitWork [hash_cap]; set 0 uses dev.work
         hipEvent_t ev_units = nullptr;      // the set's units kernel (its integrate waits for it)
         hipEvent_t ev_done = nullptr;       // the set's integrate (the set's next front end waits for it)

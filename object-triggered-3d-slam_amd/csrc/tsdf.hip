@@ -31,7 +31,7 @@ namespace ot {
 struct IntegrateParams {
     const float* depth;
     const uint8_t* color;
-    const float* mult;
+    const float* mult;  // the volume's ray-multiplier table [H][W]: gathered by the lanes that can update
     int W, H;
     float fx, fy, cx, cy;
     float E[12];
@@ -39,6 +39,7 @@ struct IntegrateParams {
     float vl, half, trunc, trunc_inv, safe_w, safe_h;
     float inv_fx, inv_fy;  // (float)(1 / (float)fx) as CreateDepthToCameraDistanceMultiplierFloatImage
     float proj_eps;  // certified fast projection: |u - rint(u)| > proj_eps decides floor and bounds exactly
+    int rcp_hi;      // FAST kernels: the largest weight + 1 of the batch (frames since reset + the batch's), <= RCP_N
     double unit_len;
 };
 
@@ -89,8 +90,8 @@ __device__ inline int hash_find(const TsdfDev& d, unsigned long long key) {
 
 // ============================================================================ batched (temporal blocking)
 // One launch per batch of F <= 64 frames:
-//   staging           : per-pixel (depth, multiplier) float2 + packed colour for every frame, done by k_batch_touch's
-//                       workgroups (each stages a contiguous pixel chunk of its frames)
+//   staging           : one 8-B record per pixel of every frame, (float depth, colour r | g << 8 | b << 16), done by
+//                       k_batch_touch's workgroups (each stages a contiguous pixel chunk of its frames)
 //   k_batch_touch     : stride samples of every frame; a unit touched by frame f gets bit f in its slot's
 //                       fmask (64-bit atomicOr); the first bit set in a batch appends the slot to bslots
 //   k_batch_units     : per touched slot: allocate the unit if new, move its frame mask into a 32-B header
@@ -98,8 +99,10 @@ __device__ inline int hash_find(const TsdfDev& d, unsigned long long key) {
 //                       loaded into registers (5 x BZ VGPRs/lane), the batch's frames are applied in call order
 //                       (ascending bits of the mask) and the state is written back once.  Per-voxel arithmetic is
 //                       the per-frame path's, so results are bit-identical to integrating frame by frame.
-// Per-pixel staging of a batch: (depth, multiplier) as float2 and the colour as one u32, so the integrate
-// kernel fetches a voxel's inputs with two aligned loads it can issue ahead of use.
+// Per-pixel staging of a batch: (depth, colour) as one 8-B record (colour word 0 for a frame without colour), so the
+// integrate kernel fetches a voxel's per-frame inputs with one aligned load it can issue ahead of use.  The ray
+// multiplier depends on the pixel and the intrinsics alone: it is not staged per frame, the integrate gathers it from
+// the volume's one table (vol->mult, IntegrateParams::mult), and only on the lanes that can update.
 // depth: u16 path converted exactly as Image::ConvertDepthToFloatImage; float path copied.
 __device__ inline float prep_depth(const BatchFrame& fr, uint32_t raw16) {
     float dv = (float)raw16;
@@ -108,9 +111,21 @@ __device__ inline float prep_depth(const BatchFrame& fr, uint32_t raw16) {
     return dv;
 }
 
-// 4 pixels per lane: 8-B depth load, 12-B colour load (3 aligned dwords), 16-B multiplier load,
-// 2 x 16-B (depth, multiplier) stores and one 16-B colour store.
-__device__ inline void prep_quad(const BatchFrame& fr, const float* __restrict__ mult, int64_t i0, int64_t npx) {
+// the staged records of 4 consecutive pixels (depths d, the 12 colour bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3 as
+// three words; zeros without colour): two 16-B stores
+__device__ inline void store_quad(uint2* dc, float d0, float d1, float d2, float d3, uint32_t w0, uint32_t w1,
+                                  uint32_t w2) {
+    const uint32_t p0 = w0 & 0xFFFFFFu;
+    const uint32_t p1 = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+    const uint32_t p2 = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+    const uint32_t p3 = w2 >> 8;
+    uint4* q = reinterpret_cast<uint4*>(dc);
+    q[0] = make_uint4(__float_as_uint(d0), p0, __float_as_uint(d1), p1);
+    q[1] = make_uint4(__float_as_uint(d2), p2, __float_as_uint(d3), p3);
+}
+
+// 4 pixels per lane: 8-B depth load, 12-B colour load (3 aligned dwords), 2 x 16-B (depth, colour) stores.
+__device__ inline void prep_quad(const BatchFrame& fr, int64_t i0, int64_t npx) {
     const bool aligned = ((reinterpret_cast<uintptr_t>(fr.depth16) & 7) == 0) &&
                          ((reinterpret_cast<uintptr_t>(fr.depthf) & 15) == 0) &&
                          ((reinterpret_cast<uintptr_t>(fr.color) & 3) == 0);
@@ -126,31 +141,21 @@ __device__ inline void prep_quad(const BatchFrame& fr, const float* __restrict__
             const float4 v = *reinterpret_cast<const float4*>(fr.depthf + i0);
             d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
         }
-        const float4 m = *reinterpret_cast<const float4*>(mult + i0);
         uint32_t w0 = 0u, w1 = 0u, w2 = 0u;  // colour loaded before the stores (char data may alias them)
         if (fr.color) {
             const uint32_t* c = reinterpret_cast<const uint32_t*>(fr.color + i0 * 3);  // 12 B, 4-B aligned
             w0 = c[0], w1 = c[1], w2 = c[2];
         }
-        float4* dm = reinterpret_cast<float4*>(fr.dm + i0);
-        dm[0] = make_float4(d[0], m.x, d[1], m.y);
-        dm[1] = make_float4(d[2], m.z, d[3], m.w);
-        if (fr.color) {
-            // bytes: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
-            const uint32_t p0 = w0 & 0xFFFFFFu;
-            const uint32_t p1 = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
-            const uint32_t p2 = (w1 >> 16) | ((w2 & 0xFFu) << 16);
-            const uint32_t p3 = w2 >> 8;
-            *reinterpret_cast<uint4*>(fr.rgba + i0) = make_uint4(p0, p1, p2, p3);
-        }
+        store_quad(fr.dc + i0, d[0], d[1], d[2], d[3], w0, w1, w2);
     } else {
         for (int64_t i = i0; i < npx && i < i0 + 4; ++i) {
             const float dv = fr.depth16 ? prep_depth(fr, fr.depth16[i]) : fr.depthf[i];
-            fr.dm[i] = make_float2(dv, mult[i]);
+            uint32_t cw = 0u;
             if (fr.color) {
                 const uint8_t* c = fr.color + i * 3;
-                fr.rgba[i] = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16);
+                cw = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16);
             }
+            fr.dc[i] = make_uint2(__float_as_uint(dv), cw);
         }
     }
 }
@@ -158,21 +163,18 @@ __device__ inline void prep_quad(const BatchFrame& fr, const float* __restrict__
 // Quads [q, q1) with stride 256 (one lane's share of a chunk): on the common path (u16 depth, RGB8, aligned, W*H
 // a multiple of 4) PREP_K quads per step with all of their loads issued before any store.
 constexpr int PREP_K = 2;  // 3 or 4 (more VGPRs, fewer resident touch waves): step +2-3 %
-__device__ inline void prep_range(const BatchFrame& fr, const float* __restrict__ mult, int64_t q, int64_t q1,
-                                  int64_t npx) {
+__device__ inline void prep_range(const BatchFrame& fr, int64_t q, int64_t q1, int64_t npx) {
     const bool fast = fr.depth16 && fr.color && (npx & 3) == 0 &&
                       ((reinterpret_cast<uintptr_t>(fr.depth16) & 7) == 0) &&
                       ((reinterpret_cast<uintptr_t>(fr.color) & 3) == 0);
     if (fast) {
         for (; q + 256 * (PREP_K - 1) < q1; q += 256 * PREP_K) {
             uint2 raw[PREP_K];
-            float4 m[PREP_K];
             uint32_t w[PREP_K][3];
 #pragma unroll
             for (int k = 0; k < PREP_K; ++k) {
                 const int64_t i0 = (q + 256 * k) * 4;
                 raw[k] = *reinterpret_cast<const uint2*>(fr.depth16 + i0);
-                m[k] = *reinterpret_cast<const float4*>(mult + i0);
                 const uint32_t* c = reinterpret_cast<const uint32_t*>(fr.color + i0 * 3);
                 w[k][0] = c[0], w[k][1] = c[1], w[k][2] = c[2];
             }
@@ -181,18 +183,11 @@ __device__ inline void prep_range(const BatchFrame& fr, const float* __restrict_
                 const int64_t i0 = (q + 256 * k) * 4;
                 const float d0 = prep_depth(fr, raw[k].x & 0xFFFFu), d1 = prep_depth(fr, raw[k].x >> 16);
                 const float d2 = prep_depth(fr, raw[k].y & 0xFFFFu), d3 = prep_depth(fr, raw[k].y >> 16);
-                float4* dm = reinterpret_cast<float4*>(fr.dm + i0);
-                dm[0] = make_float4(d0, m[k].x, d1, m[k].y);
-                dm[1] = make_float4(d2, m[k].z, d3, m[k].w);
-                const uint32_t p0 = w[k][0] & 0xFFFFFFu;
-                const uint32_t p1 = (w[k][0] >> 24) | ((w[k][1] & 0xFFFFu) << 8);
-                const uint32_t p2 = (w[k][1] >> 16) | ((w[k][2] & 0xFFu) << 16);
-                const uint32_t p3 = w[k][2] >> 8;
-                *reinterpret_cast<uint4*>(fr.rgba + i0) = make_uint4(p0, p1, p2, p3);
+                store_quad(fr.dc + i0, d0, d1, d2, d3, w[k][0], w[k][1], w[k][2]);
             }
         }
     }
-    for (; q < q1; q += 256) prep_quad(fr, mult, q * 4, npx);
+    for (; q < q1; q += 256) prep_quad(fr, q * 4, npx);
 }
 
 // The batch's per-frame parameters from the pinned host staging into device memory: one small kernel reading host
@@ -214,13 +209,12 @@ struct BatchTouchParams {
     double trunc, unit_len;
     double inv_unit;    // RN(1 / unit_len): floor_div's certified product
     int slot_cap;
-    const float* mult;  // fused staging (k_batch_touch stages the batch's pixels too): ray multipliers
-    int64_t npx;        // pixels per frame
+    int64_t npx;        // pixels per frame (fused staging: k_batch_touch stages the batch's pixels too)
     int pc;             // this batch's pair counter index
     int tiles;          // touch workgroups per frame group (blockIdx.x below it)
     int stage_blocks;   // staging-only workgroups per frame group after them (0: each touch workgroup stages a share)
     int tf;             // frames per group (TF)
-    int sample_stage;   // split front end (stage_blocks < 0): each stride sample stores its own pixel's staged pair
+    int sample_stage;   // split front end (stage_blocks < 0): each stride sample stores its own pixel's staged record
                         // (a replay touch reads it; k_stage_tiles stages only the owned units' footprints)
 };
 
@@ -295,7 +289,7 @@ __device__ inline void stage_share(const BatchFrame* __restrict__ frames, const 
     const int64_t per = (quads + parts - 1) / parts;
     const int64_t q0 = (int64_t)part * per, q1 = q0 + per < quads ? q0 + per : quads;
     for (int f = grp * p.tf; f < grp * p.tf + p.tf && f < nframes; ++f)
-        prep_range(frames[f], p.mult, q0 + threadIdx.x, q1, p.npx);
+        prep_range(frames[f], q0 + threadIdx.x, q1, p.npx);
 }
 
 // Staging (every pixel of the batch: HBM streaming) and the touch (stride samples: LDS merges and global hash atomics)
@@ -352,9 +346,18 @@ __device__ __forceinline__ void touch_body(const BatchFrame* __restrict__ frames
         for (int f = f0; f < f0 + p.tf && f < nframes; ++f) {
             const BatchFrame& fr = frames[f];
             const int64_t pix = (int64_t)r * p.W + c;  // the staged depth, computed as the staging does
-            const float df = REPLAY ? fr.dm[pix].x : fr.depth16 ? prep_depth(fr, fr.depth16[pix]) : fr.depthf[pix];
+            const float df = REPLAY           ? __uint_as_float(fr.dc[pix].x)
+                             : fr.depth16 ? prep_depth(fr, fr.depth16[pix])
+                                          : fr.depthf[pix];
             if constexpr (!REPLAY) {
-                if (p.sample_stage) fr.dm[pix] = make_float2(df, p.mult[pix]);  // what the staging writes there
+                if (p.sample_stage) {  // what the staging writes there
+                    uint32_t cw = 0u;
+                    if (fr.color) {
+                        const uint8_t* c = fr.color + pix * 3;
+                        cw = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16);
+                    }
+                    fr.dc[pix] = make_uint2(__float_as_uint(df), cw);
+                }
             }
             if (!(df > 0.0f)) continue;
             const double z = (double)df;
@@ -687,7 +690,7 @@ __global__ __launch_bounds__(256) void k_stage_mask(const BatchFrame* __restrict
 // twice writes the same bytes.
 constexpr int ST_MAX_TILES_X = 256;
 constexpr int ST_K = 4;  // quads per lane per step on the common path
-__global__ __launch_bounds__(256) void k_stage_tiles(const BatchFrame* __restrict__ frames, const float* __restrict__ mult,
+__global__ __launch_bounds__(256) void k_stage_tiles(const BatchFrame* __restrict__ frames,
                                                      const unsigned* __restrict__ mask, int W, int H, int tiles_x,
                                                      int tiles_y, int wpr, int64_t npx) {
     __shared__ int s_tx[ST_MAX_TILES_X];
@@ -718,7 +721,6 @@ __global__ __launch_bounds__(256) void k_stage_tiles(const BatchFrame* __restric
         for (int i0 = threadIdx.x; i0 < total; i0 += 256 * ST_K) {
             int64_t px[ST_K];
             uint2 raw[ST_K];
-            float4 mv[ST_K];
             uint32_t w[ST_K][3];
 #pragma unroll
             for (int k = 0; k < ST_K; ++k) {
@@ -729,7 +731,6 @@ __global__ __launch_bounds__(256) void k_stage_tiles(const BatchFrame* __restric
                 if (i < total && x < W) {  // (the frame's last tile column may be narrower than STX)
                     px[k] = (int64_t)r * W + x;
                     raw[k] = *reinterpret_cast<const uint2*>(fr.depth16 + px[k]);
-                    mv[k] = *reinterpret_cast<const float4*>(mult + px[k]);
                     const uint32_t* c = reinterpret_cast<const uint32_t*>(fr.color + px[k] * 3);
                     w[k][0] = c[0], w[k][1] = c[1], w[k][2] = c[2];
                 }
@@ -739,14 +740,7 @@ __global__ __launch_bounds__(256) void k_stage_tiles(const BatchFrame* __restric
                 if (px[k] < 0) continue;
                 const float d0 = prep_depth(fr, raw[k].x & 0xFFFFu), d1 = prep_depth(fr, raw[k].x >> 16);
                 const float d2 = prep_depth(fr, raw[k].y & 0xFFFFu), d3 = prep_depth(fr, raw[k].y >> 16);
-                float4* dm = reinterpret_cast<float4*>(fr.dm + px[k]);
-                dm[0] = make_float4(d0, mv[k].x, d1, mv[k].y);
-                dm[1] = make_float4(d2, mv[k].z, d3, mv[k].w);
-                const uint32_t p0 = w[k][0] & 0xFFFFFFu;
-                const uint32_t p1 = (w[k][0] >> 24) | ((w[k][1] & 0xFFFFu) << 8);
-                const uint32_t p2 = (w[k][1] >> 16) | ((w[k][2] & 0xFFu) << 16);
-                const uint32_t p3 = w[k][2] >> 8;
-                *reinterpret_cast<uint4*>(fr.rgba + px[k]) = make_uint4(p0, p1, p2, p3);
+                store_quad(fr.dc + px[k], d0, d1, d2, d3, w[k][0], w[k][1], w[k][2]);
             }
         }
         return;
@@ -756,7 +750,7 @@ __global__ __launch_bounds__(256) void k_stage_tiles(const BatchFrame* __restric
         const int r = y0 + rem / slots, kq = rem - (rem / slots) * slots;
         const int x0 = s_tx[t] * STX, x1 = min(W, x0 + STX);
         const int64_t qa = ((int64_t)r * W + x0) >> 2, qb = ((int64_t)r * W + x1 - 1) >> 2;
-        if (qa + kq <= qb) prep_quad(fr, mult, (qa + kq) * 4, npx);
+        if (qa + kq <= qb) prep_quad(fr, (qa + kq) * 4, npx);
     }
 }
 
@@ -785,8 +779,8 @@ __device__ __forceinline__ bool static_all(F& f) {
 template <int ZB>
 __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateParams& p, int npx, float px, float py,
                                           float pz, int z0, int (&pixv)[ZB], float (&pcz)[ZB], float (&dv)[ZB],
-                                          float (&mv)[ZB]) {
-    const __amdgpu_buffer_rsrc_t dm_rsrc = make_rsrc(fr.dm, npx * 8);
+                                          uint32_t (&cv)[ZB]) {
+    const __amdgpu_buffer_rsrc_t dc_rsrc = make_rsrc(fr.dc, npx * 8);
     float pc[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -822,11 +816,12 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
     }
 #pragma unroll
     for (int k = 0; k < ZB; ++k) {
-        dv[k] = mv[k] = 0.0f;
+        dv[k] = 0.0f;
+        cv[k] = 0u;
         if (pixv[k] >= 0) {
-            const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dm_rsrc, pixv[k] * 8, 0, 0);
+            const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, pixv[k] * 8, 0, 0);
             dv[k] = __uint_as_float(raw.x);
-            mv[k] = __uint_as_float(raw.y);
+            cv[k] = raw.y;
         }
     }
 }
@@ -880,7 +875,7 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
         if (bid >= (PARTS == 1 ? n0 : ((n0 + 7) / 8) * 8 * PARTS)) return;
     }
     if constexpr (FAST) {
-        for (int r = threadIdx.x; r <= RCP_N; r += 64 * INT_WG) {
+        for (int r = 1 + threadIdx.x; r <= p.rcp_hi; r += 64 * INT_WG) {  // entries 1 .. the batch's largest weight + 1
             if constexpr (C64) s_r64[r] = 1.0 / (double)r;  // IEEE (correctly rounded) quotients
             else s_r32[r] = 1.0f / (float)r;
         }
@@ -946,9 +941,10 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
                 if constexpr (ZB == 2) {
                     // Frame pipeline (the fine slices serve batches with few units, whose waves cannot hide a frame's
                     // dependent gathers behind other waves: the wave's chain of frames IS the batch's time).  Every
-                    // load of a frame is state-independent -- the projections and depth gathers (tap), the depth test,
-                    // clamped tsdf term and colour gather (stage C) -- only the running means (stage D) read the
-                    // voxel state.  So frame f+KT's tap and frame f+KC's stage C are issued before frame f's update,
+                    // load of a frame is state-independent -- the projections and (depth, colour) gathers (tap), the
+                    // candidate test on d - z and the multiplier gather (stage C) -- only the update test on the scaled
+                    // distance, the clamped term and the running means (stage D) wait for it and read the voxel state.
+                    // So frame f+KT's tap and frame f+KC's stage C are issued before frame f's update,
                     // from KT + 1 register slots (the loop is unrolled over the slots so every slot is a fixed
                     // register set: a rotating copy would wait for the loads in flight).  The updates still run in
                     // frame order with the same arithmetic: the bits are the unpipelined loop's.  KT = 1, KC = 0 is the
@@ -957,16 +953,16 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
                     unsigned long long mt = mask;  // frames not yet tapped
                     int fs[RS];                     // frame of each slot (wave-uniform), -1: past the last frame
                     int pixv[RS][ZB];
-                    float pcz[RS][ZB], dv[RS][ZB], mv[RS][ZB], tnv[RS][ZB];
+                    float pcz[RS][ZB], dv[RS][ZB], mv[RS][ZB], dfv[RS][ZB];
                     uint32_t cv[RS][ZB];
-                    bool dov[RS][ZB];
+                    bool cav[RS][ZB];
                     auto tap = [&](auto J) __attribute__((always_inline)) {
                         constexpr int j = decltype(J)::value;
                         if (mt) {
                             const int f = __ffsll((long long)mt) - 1;
                             mt &= mt - 1;
                             fs[j] = f;
-                            frame_tap<ZB>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], mv[j]);
+                            frame_tap<ZB>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
                         } else {
                             fs[j] = -1;
                         }
@@ -974,18 +970,17 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
                     auto stage_c = [&](auto J) __attribute__((always_inline)) {
                         constexpr int j = decltype(J)::value;
                         if (fs[j] < 0) return;
-                        const BatchFrame& fr = frames[fs[j]];
-                        const __amdgpu_buffer_rsrc_t rgba_rsrc = make_rsrc(fr.rgba, npx * 4);
-                        const bool use_color = fr.color != nullptr;
+                        // candidates: the multiplier is >= 1, so (d - z) * m > -trunc implies d - z > -trunc -- only
+                        // these lanes gather it, from the volume's one table (stage D makes the update test itself)
+                        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
 #pragma unroll
                         for (int k = 0; k < ZB; ++k) {
-                            const float sdf = (dv[j][k] - pcz[j][k]) * mv[j][k];
-                            dov[j][k] = (pixv[j][k] >= 0) & (dv[j][k] > 0.0f) & (sdf > -p.trunc);
-                            const float sv = sdf * p.trunc_inv;
-                            tnv[j][k] = (sv < 1.0f) ? sv : 1.0f;
-                            cv[j][k] = 0u;
-                            if (use_color && dov[j][k])
-                                cv[j][k] = __builtin_amdgcn_raw_buffer_load_b32(rgba_rsrc, pixv[j][k] * 4, 0, 0);
+                            dfv[j][k] = dv[j][k] - pcz[j][k];
+                            cav[j][k] = (pixv[j][k] >= 0) & (dv[j][k] > 0.0f) & (dfv[j][k] > -p.trunc);
+                            mv[j][k] = 0.0f;
+                            if (cav[j][k])
+                                mv[j][k] = __uint_as_float(
+                                    __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, pixv[j][k] * 4, 0, 0));
                         }
                     };
                     auto stage_d = [&](auto J) __attribute__((always_inline)) -> bool {
@@ -994,8 +989,10 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
                         const bool use_color = frames[fs[j]].color != nullptr;
 #pragma unroll
                         for (int k = 0; k < ZB; ++k) {
-                            const bool doit = dov[j][k];
-                            const float tn = tnv[j][k];
+                            const float sdf = dfv[j][k] * mv[j][k];
+                            const bool doit = cav[j][k] & (sdf > -p.trunc);
+                            const float sv = sdf * p.trunc_inv;
+                            const float tn = (sv < 1.0f) ? sv : 1.0f;
                             const float wv = wt[k];
                             const float w1 = wv + 1.0f;
                             const float ta = ts[k] * wv + tn;
@@ -1063,15 +1060,20 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
                     for (unsigned long long m = mask; m; m &= m - 1) {
                         const int f = __ffsll((long long)m) - 1;
                         const BatchFrame& fr = frames[f];
-                        const __amdgpu_buffer_rsrc_t dm_rsrc = make_rsrc(fr.dm, npx * 8);
-                        const __amdgpu_buffer_rsrc_t rgba_rsrc = make_rsrc(fr.rgba, npx * 4);
+                        const __amdgpu_buffer_rsrc_t dc_rsrc = make_rsrc(fr.dc, npx * 8);
+                        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
                         const bool use_color = fr.color != nullptr;
                         float pc[3];
+                        // per-frame copies of the voxel column's position: the compiler pairs the rows' products
+                        // (packed float32 math) and would otherwise keep px, py, pz duplicated in register pairs across
+                        // the whole frame loop (8 VGPRs for 3 values: the float64-colour kernel then spills)
+                        float fpx = px, fpy = py, fpz = pz;
+                        asm volatile("" : "+v"(fpx), "+v"(fpy), "+v"(fpz));
 #pragma unroll
                         for (int r = 0; r < 3; ++r) {
-                            const float a = fr.E[r * 4 + 0] * px;
-                            const float b = fr.E[r * 4 + 1] * py;
-                            const float c = fr.E[r * 4 + 2] * pz;
+                            const float a = fr.E[r * 4 + 0] * fpx;
+                            const float b = fr.E[r * 4 + 1] * fpy;
+                            const float c = fr.E[r * 4 + 2] * fpz;
                             pc[r] = ((a + b) + c) + fr.E[r * 4 + 3];
                         }
                         const float es0 = fr.es[0], es1 = fr.es[1], es2 = fr.es[2];
@@ -1111,32 +1113,38 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
                         }
                         // phase B: every depth gather issued before any use (buffer loads: wave-uniform resource +
                         // 32-bit byte offset, no per-lane 64-bit address math)
-                        float dv[ZB], mv[ZB];
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            dv[k] = mv[k] = 0.0f;
-                            if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
-                                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dm_rsrc, pixv[k] * 8, 0, 0);
-                                dv[k] = __uint_as_float(raw.x);
-                                mv[k] = __uint_as_float(raw.y);
-                            }
-                        }
-                        // phase C: the depth test; colour gathered only by the lanes whose voxel updates
-                        bool doitv[ZB];
-                        float sdfv[ZB];
+                        float dv[ZB];
                         uint32_t cv[ZB];
 #pragma unroll
                         for (int k = 0; k < ZB; ++k) {
-                            sdfv[k] = (dv[k] - pcz[k]) * mv[k];
-                            doitv[k] = (pixv[k] >= 0) & (dv[k] > 0.0f) & (sdfv[k] > -p.trunc);
+                            dv[k] = 0.0f;
                             cv[k] = 0u;
-                            if (use_color && doitv[k]) cv[k] = __builtin_amdgcn_raw_buffer_load_b32(rgba_rsrc, pixv[k] * 4, 0, 0);
+                            if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
+                                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, pixv[k] * 8, 0, 0);
+                                dv[k] = __uint_as_float(raw.x);
+                                cv[k] = raw.y;
+                            }
+                        }
+                        // phase C: the depth test.  The ray multiplier (the volume's one table, not a per-frame copy)
+                        // is gathered only by the candidate lanes: it is >= 1 and rounding is monotone, so
+                        // (d - z) * m > -trunc implies d - z > -trunc; the test on the product is then Open3D's
+                        bool doitv[ZB];
+                        float sdfv[ZB];
+                        unsigned mv[ZB];  // the gather's byte offset, then its result in the same register (the other
+                                          // lanes keep the offset: their product is never selected)
+#pragma unroll
+                        for (int k = 0; k < ZB; ++k) {
+                            sdfv[k] = dv[k] - pcz[k];
+                            doitv[k] = (pixv[k] >= 0) & (dv[k] > 0.0f) & (sdfv[k] > -p.trunc);
+                            mv[k] = (unsigned)pixv[k] * 4u;
+                            if (doitv[k]) mv[k] = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, (int)mv[k], 0, 0);
                         }
                         // phase D: updates in frame order (select form: identical values, no exec-mask branches)
 #pragma unroll
                         for (int k = 0; k < ZB; ++k) {
-                            const bool doit = doitv[k];
-                            const float sv = sdfv[k] * p.trunc_inv;
+                            const float sdf = sdfv[k] * __uint_as_float(mv[k]);
+                            const bool doit = doitv[k] & (sdf > -p.trunc);
+                            const float sv = sdf * p.trunc_inv;
                             const float tn = (sv < 1.0f) ? sv : 1.0f;
                             const float wv = wt[k];
                             const float w1 = wv + 1.0f;
@@ -1237,7 +1245,7 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : IN
         if ((int)blockIdx.x >= (PARTS == 1 ? n0 : ((n0 + 7) / 8) * 8 * PARTS)) return;
     }
     if constexpr (FAST) {
-        for (int r = threadIdx.x; r <= RCP_N; r += 64 * INT_WG) {
+        for (int r = 1 + threadIdx.x; r <= p.rcp_hi; r += 64 * INT_WG) {  // entries 1 .. the batch's largest weight + 1
             if constexpr (C64) s_r64[r] = 1.0 / (double)r;  // IEEE (correctly rounded) quotients
             else s_r32[r] = 1.0f / (float)r;
         }
@@ -1302,9 +1310,10 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : IN
                 if constexpr (ZB == 2) {
                     // Frame pipeline (the fine slices serve batches with few units, whose waves cannot hide a frame's
                     // dependent gathers behind other waves: the wave's chain of frames IS the batch's time).  Every
-                    // load of a frame is state-independent -- the projections and depth gathers (tap), the depth test,
-                    // clamped tsdf term and colour gather (stage C) -- only the running means (stage D) read the
-                    // voxel state.  So frame f+KT's tap and frame f+KC's stage C are issued before frame f's update,
+                    // load of a frame is state-independent -- the projections and (depth, colour) gathers (tap), the
+                    // candidate test on d - z and the multiplier gather (stage C) -- only the update test on the scaled
+                    // distance, the clamped term and the running means (stage D) wait for it and read the voxel state.
+                    // So frame f+KT's tap and frame f+KC's stage C are issued before frame f's update,
                     // from KT + 1 register slots (the loop is unrolled over the slots so every slot is a fixed
                     // register set: a rotating copy would wait for the loads in flight).  The updates still run in
                     // frame order with the same arithmetic: the bits are the unpipelined loop's.  KT = 1, KC = 0 is the
@@ -1313,16 +1322,16 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : IN
                     unsigned long long mt = mask;  // frames not yet tapped
                     int fs[RS];                     // frame of each slot (wave-uniform), -1: past the last frame
                     int pixv[RS][ZB];
-                    float pcz[RS][ZB], dv[RS][ZB], mv[RS][ZB], tnv[RS][ZB];
+                    float pcz[RS][ZB], dv[RS][ZB], mv[RS][ZB], dfv[RS][ZB];
                     uint32_t cv[RS][ZB];
-                    bool dov[RS][ZB];
+                    bool cav[RS][ZB];
                     auto tap = [&](auto J) __attribute__((always_inline)) {
                         constexpr int j = decltype(J)::value;
                         if (mt) {
                             const int f = __ffsll((long long)mt) - 1;
                             mt &= mt - 1;
                             fs[j] = f;
-                            frame_tap<ZB>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], mv[j]);
+                            frame_tap<ZB>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
                         } else {
                             fs[j] = -1;
                         }
@@ -1330,18 +1339,17 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : IN
                     auto stage_c = [&](auto J) __attribute__((always_inline)) {
                         constexpr int j = decltype(J)::value;
                         if (fs[j] < 0) return;
-                        const BatchFrame& fr = frames[fs[j]];
-                        const __amdgpu_buffer_rsrc_t rgba_rsrc = make_rsrc(fr.rgba, npx * 4);
-                        const bool use_color = fr.color != nullptr;
+                        // candidates: the multiplier is >= 1, so (d - z) * m > -trunc implies d - z > -trunc -- only
+                        // these lanes gather it, from the volume's one table (stage D makes the update test itself)
+                        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
 #pragma unroll
                         for (int k = 0; k < ZB; ++k) {
-                            const float sdf = (dv[j][k] - pcz[j][k]) * mv[j][k];
-                            dov[j][k] = (pixv[j][k] >= 0) & (dv[j][k] > 0.0f) & (sdf > -p.trunc);
-                            const float sv = sdf * p.trunc_inv;
-                            tnv[j][k] = (sv < 1.0f) ? sv : 1.0f;
-                            cv[j][k] = 0u;
-                            if (use_color && dov[j][k])
-                                cv[j][k] = __builtin_amdgcn_raw_buffer_load_b32(rgba_rsrc, pixv[j][k] * 4, 0, 0);
+                            dfv[j][k] = dv[j][k] - pcz[j][k];
+                            cav[j][k] = (pixv[j][k] >= 0) & (dv[j][k] > 0.0f) & (dfv[j][k] > -p.trunc);
+                            mv[j][k] = 0.0f;
+                            if (cav[j][k])
+                                mv[j][k] = __uint_as_float(
+                                    __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, pixv[j][k] * 4, 0, 0));
                         }
                     };
                     auto stage_d = [&](auto J) __attribute__((always_inline)) -> bool {
@@ -1350,8 +1358,10 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : IN
                         const bool use_color = frames[fs[j]].color != nullptr;
 #pragma unroll
                         for (int k = 0; k < ZB; ++k) {
-                            const bool doit = dov[j][k];
-                            const float tn = tnv[j][k];
+                            const float sdf = dfv[j][k] * mv[j][k];
+                            const bool doit = cav[j][k] & (sdf > -p.trunc);
+                            const float sv = sdf * p.trunc_inv;
+                            const float tn = (sv < 1.0f) ? sv : 1.0f;
                             const float wv = wt[k];
                             const float w1 = wv + 1.0f;
                             const float ta = ts[k] * wv + tn;
@@ -1419,15 +1429,20 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : IN
                     for (unsigned long long m = mask; m; m &= m - 1) {
                         const int f = __ffsll((long long)m) - 1;
                         const BatchFrame& fr = frames[f];
-                        const __amdgpu_buffer_rsrc_t dm_rsrc = make_rsrc(fr.dm, npx * 8);
-                        const __amdgpu_buffer_rsrc_t rgba_rsrc = make_rsrc(fr.rgba, npx * 4);
+                        const __amdgpu_buffer_rsrc_t dc_rsrc = make_rsrc(fr.dc, npx * 8);
+                        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
                         const bool use_color = fr.color != nullptr;
                         float pc[3];
+                        // per-frame copies of the voxel column's position: the compiler pairs the rows' products
+                        // (packed float32 math) and would otherwise keep px, py, pz duplicated in register pairs across
+                        // the whole frame loop (8 VGPRs for 3 values: the float64-colour kernel then spills)
+                        float fpx = px, fpy = py, fpz = pz;
+                        asm volatile("" : "+v"(fpx), "+v"(fpy), "+v"(fpz));
 #pragma unroll
                         for (int r = 0; r < 3; ++r) {
-                            const float a = fr.E[r * 4 + 0] * px;
-                            const float b = fr.E[r * 4 + 1] * py;
-                            const float c = fr.E[r * 4 + 2] * pz;
+                            const float a = fr.E[r * 4 + 0] * fpx;
+                            const float b = fr.E[r * 4 + 1] * fpy;
+                            const float c = fr.E[r * 4 + 2] * fpz;
                             pc[r] = ((a + b) + c) + fr.E[r * 4 + 3];
                         }
                         const float es0 = fr.es[0], es1 = fr.es[1], es2 = fr.es[2];
@@ -1467,32 +1482,38 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : IN
                         }
                         // phase B: every depth gather issued before any use (buffer loads: wave-uniform resource +
                         // 32-bit byte offset, no per-lane 64-bit address math)
-                        float dv[ZB], mv[ZB];
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            dv[k] = mv[k] = 0.0f;
-                            if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
-                                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dm_rsrc, pixv[k] * 8, 0, 0);
-                                dv[k] = __uint_as_float(raw.x);
-                                mv[k] = __uint_as_float(raw.y);
-                            }
-                        }
-                        // phase C: the depth test; colour gathered only by the lanes whose voxel updates
-                        bool doitv[ZB];
-                        float sdfv[ZB];
+                        float dv[ZB];
                         uint32_t cv[ZB];
 #pragma unroll
                         for (int k = 0; k < ZB; ++k) {
-                            sdfv[k] = (dv[k] - pcz[k]) * mv[k];
-                            doitv[k] = (pixv[k] >= 0) & (dv[k] > 0.0f) & (sdfv[k] > -p.trunc);
+                            dv[k] = 0.0f;
                             cv[k] = 0u;
-                            if (use_color && doitv[k]) cv[k] = __builtin_amdgcn_raw_buffer_load_b32(rgba_rsrc, pixv[k] * 4, 0, 0);
+                            if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
+                                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, pixv[k] * 8, 0, 0);
+                                dv[k] = __uint_as_float(raw.x);
+                                cv[k] = raw.y;
+                            }
+                        }
+                        // phase C: the depth test.  The ray multiplier (the volume's one table, not a per-frame copy)
+                        // is gathered only by the candidate lanes: it is >= 1 and rounding is monotone, so
+                        // (d - z) * m > -trunc implies d - z > -trunc; the test on the product is then Open3D's
+                        bool doitv[ZB];
+                        float sdfv[ZB];
+                        unsigned mv[ZB];  // the gather's byte offset, then its result in the same register (the other
+                                          // lanes keep the offset: their product is never selected)
+#pragma unroll
+                        for (int k = 0; k < ZB; ++k) {
+                            sdfv[k] = dv[k] - pcz[k];
+                            doitv[k] = (pixv[k] >= 0) & (dv[k] > 0.0f) & (sdfv[k] > -p.trunc);
+                            mv[k] = (unsigned)pixv[k] * 4u;
+                            if (doitv[k]) mv[k] = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, (int)mv[k], 0, 0);
                         }
                         // phase D: updates in frame order (select form: identical values, no exec-mask branches)
 #pragma unroll
                         for (int k = 0; k < ZB; ++k) {
-                            const bool doit = doitv[k];
-                            const float sv = sdfv[k] * p.trunc_inv;
+                            const float sdf = sdfv[k] * __uint_as_float(mv[k]);
+                            const bool doit = doitv[k] & (sdf > -p.trunc);
+                            const float sv = sdf * p.trunc_inv;
                             const float tn = (sv < 1.0f) ? sv : 1.0f;
                             const float wv = wt[k];
                             const float w1 = wv + 1.0f;
@@ -1956,13 +1977,20 @@ static IntegrateParams make_integrate_params(const ot_tsdf* vol, const float* de
     // |fast u - IEEE u| <= 2^-21 (max(W, H) + 2) on [-1, W + 1] (rcp 1 ulp, four roundings); the bound tests sit
     // 1e-4 from integers, so any margin above both keeps every decision identical (see k_batch_integrate)
     p.proj_eps = (float)(std::ldexp((double)std::max(in->width, in->height) + 2.0, -21) + 1.2e-4);
+    p.rcp_hi = RCP_N;  // (integrate_batch narrows it to the batch)
     p.unit_len = vol->unit_length;
     return p;
 }
 
+struct BatchCtx;
+static ot_status launch_deferred(ot_tsdf* vol, hipStream_t stream, const BatchCtx* next);
 static ot_status ensure_mult(ot_tsdf* vol, const ot_intrinsics* in, hipStream_t stream) {
     if (vol->mult_valid && std::memcmp(&vol->mult_intr, in, sizeof(ot_intrinsics)) == 0) return OT_OK;
     if (vol->mult) {
+        // the integrate reads the table: a deferred batch's runs first, one on the integrate stream is waited for
+        ot_status sd = launch_deferred(vol, stream, nullptr);
+        if (sd != OT_OK) return sd;
+        if (vol->istream) OT_HIP_TRY(hipStreamSynchronize(vol->istream));
         OT_HIP_TRY(hipStreamSynchronize(stream));
         OT_HIP_TRY(hipFree(vol->mult));
         vol->mult = nullptr;
@@ -2084,10 +2112,10 @@ static ot_status ensure_tmask(ot_tsdf* vol, int w, int h, hipStream_t stream) {
 }
 // mark the tiles the units of the work list (`wcount` entries) project to, then stage those tiles
 static void launch_stage(const BatchFrame* bf, const StageMaskParams& q, const UnitWork* work, const int* wcount,
-                         unsigned* smask, const float* mult, hipStream_t stream) {
+                         unsigned* smask, hipStream_t stream) {
     hipLaunchKernelGGL(k_stage_mask, dim3((unsigned)q.nframes, SM_PARTS), dim3(256), 0, stream, bf, q, work, wcount,
                        smask);
-    hipLaunchKernelGGL(k_stage_tiles, dim3((unsigned)q.tiles_y, (unsigned)q.nframes), dim3(256), 0, stream, bf, mult,
+    hipLaunchKernelGGL(k_stage_tiles, dim3((unsigned)q.tiles_y, (unsigned)q.nframes), dim3(256), 0, stream, bf,
                        (const unsigned*)smask, q.W, q.H, q.tiles_x, q.tiles_y, q.wpr, (int64_t)q.W * q.H);
 }
 static void* set_work(ot_tsdf* vol, int s) { return s == 0 ? vol->dev.work : vol->bset[1].work; }
@@ -2209,17 +2237,14 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
     if (ovl) OT_HIP_TRY(hipStreamWaitEvent(stream, bs.ev_done, 0));
     const int64_t npx = (int64_t)in.width * in.height;
     if (bs.cap < npx * n) {
-        if (bs.bdm) {
+        if (bs.bdc) {
             OT_HIP_TRY(hipStreamSynchronize(stream));
             if (vol->istream) OT_HIP_TRY(hipStreamSynchronize(vol->istream));
-            OT_HIP_TRY(hipFree(bs.bdm));
-            OT_HIP_TRY(hipFree(bs.brgba));
-            bs.bdm = nullptr;
-            bs.brgba = nullptr;
+            OT_HIP_TRY(hipFree(bs.bdc));
+            bs.bdc = nullptr;
         }
         const int64_t cap = npx * std::max(n, std::min(vol->batch_max, MAX_BATCH));
-        OT_HIP_TRY(hipMalloc(&bs.bdm, sizeof(float2) * cap));
-        OT_HIP_TRY(hipMalloc(&bs.brgba, sizeof(uint32_t) * cap));
+        OT_HIP_TRY(hipMalloc(&bs.bdc, sizeof(uint2) * cap));
         bs.cap = cap;
     }
     // per-frame parameters: pinned host staging (double-buffered, event-guarded) -> device
@@ -2234,8 +2259,8 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
         b.depth16 = f.depth;
         b.depthf = f.depth ? nullptr : f.depthf;
         b.color = (vol->color_type == OT_COLOR_RGB8) ? f.color : nullptr;
-        b.dm = bs.bdm + npx * k;
-        b.rgba = bs.brgba + npx * k;
+        b.dc = bs.bdc + npx * k;
+        b.pad = 0;
         double pose[16];
         inverse4(f.extrinsic, pose);
         for (int i = 0; i < 12; ++i) b.pose[i] = pose[i];
@@ -2253,7 +2278,6 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
     // this batch's pair counter: zeroed by reset, or by the previous batch's k_batch_units (no memset here)
     const int pc = vol->batch_pc;
     BatchTouchParams& tp = bc.tp;
-    tp.mult = vol->mult;
     tp.npx = npx;
     tp.pc = pc;
     tp.W = in.width;
@@ -2316,13 +2340,15 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
         bc.split = true;
         bc.sq = q;
         bc.smask = vol->tmask;
-        launch_stage((const BatchFrame*)bs.bframes, q, (const UnitWork*)work, (const int*)wcount, vol->tmask,
-                     (const float*)vol->mult, stream);
+        launch_stage((const BatchFrame*)bs.bframes, q, (const UnitWork*)work, (const int*)wcount, vol->tmask, stream);
     }
     // reciprocal-table kernel while every weight + 1 is an integer <= RCP_N: weights count updates, at most one
     // per frame since reset, unless units were imported (k_batch_integrate: Markstein's exact correction)
     const bool fast = !vol->imported && (int64_t)vol->frame_id + n < RCP_N;
     bc.variant = (vol->color64 ? 2 : 0) + (fast ? 1 : 0);
+    // the table entries the batch can read: a weight is at most the frames since reset, so weight + 1 <= frame_id + n
+    // (before frame_id advances; kept in the batch's context for a deferred launch or a replay)
+    bc.ip0.rcp_hi = (int)std::min<int64_t>((int64_t)vol->frame_id + n, RCP_N);
     // Few units (a spatial shard, a small object): a (unit, quarter) item is a chain of the batch's frames, each frame
     // two dependent gather round trips plus ~270 dependent VALU instructions, so a batch too small to fill the GPU is
     // bound by that chain -- ~130 us per 64 frames whatever the unit count (tools/shard_scaling.py, r05g: rank 0 of
@@ -2526,16 +2552,14 @@ static ot_status settle_batch(ot_tsdf* vol, const BatchCtx& bc, hipStream_t stre
         if (bc.defer) {  // nothing of the batch is integrated yet: rebuild its whole work list, restage, stay deferred
             hipLaunchKernelGGL(k_batch_units<false>, dim3(256), dim3(256), 0, stream, vol->dev, work, bc.pc,
                                vol->hmail + OT_MAIL_WORDS, vol->wcount + bc.set, ++vol->units_seq);
-            launch_stage(bf, bc.sq, (const UnitWork*)work, (const int*)(vol->wcount + bc.set), bc.smask,
-                         (const float*)vol->mult, stream);
+            launch_stage(bf, bc.sq, (const UnitWork*)work, (const int*)(vol->wcount + bc.set), bc.smask, stream);
             OT_LAUNCH_CHECK();
             continue;
         }
         hipLaunchKernelGGL(k_batch_units<true>, dim3(256), dim3(256), 0, stream, vol->dev, work, bc.pc,
                            vol->hmail + OT_MAIL_WORDS, (int*)nullptr, ++vol->units_seq);
         if (bc.split) {  // the replayed units' tiles, from the caller's frames (valid until this flush returns)
-            launch_stage(bf, bc.sq, (const UnitWork*)work, (const int*)(vol->dev.counters + bc.pc), bc.smask,
-                         (const float*)vol->mult, stream);
+            launch_stage(bf, bc.sq, (const UnitWork*)work, (const int*)(vol->dev.counters + bc.pc), bc.smask, stream);
         }
         const UnitWork* uw = work;
         const int* wc = vol->dev.counters + bc.pc;
@@ -2815,8 +2839,8 @@ ot_status ot_tsdf_destroy(ot_tsdf* v) {
     ot_tsdf_set_profiling(v, 0);
     void* ptrs[] = {d.hkeys, d.hvals, d.counters, d.stats, d.unit_keys, d.vox, v->mult, v->sorted_ids, v->mesh.ws,
                     v->mesh.v, v->mesh.c, v->mesh.t, v->mesh.vk, v->mesh.tk, v->mesh.vown, d.fmask, d.bslots, d.work,
-                    v->wcount, v->bset[0].bframes, v->bset[0].bdm, v->bset[0].brgba, v->bset[1].bframes,
-                    v->bset[1].bdm, v->bset[1].brgba, v->bset[1].work, v->tmask};
+                    v->wcount, v->bset[0].bframes, v->bset[0].bdc, v->bset[1].bframes, v->bset[1].bdc,
+                    v->bset[1].work, v->tmask};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (v->hbframes) (void)hipHostFree(v->hbframes);
