@@ -773,9 +773,26 @@ __device__ __forceinline__ bool static_all(F& f) {
     }
 }
 
-// Phases A and B of one frame for a lane's ZB voxels: the certified projections and the depth gathers (no voxel state
-// read) -- the fine slices' frame skew issues them for frame f+1 before frame f's updates (k_batch_integrate).  The same
-// arithmetic as the phases inside the coarse loop.
+// Occupancy: the integrate lives on it (DESIGN.md §4): 64 VGPRs, 8 waves per SIMD for both colour precisions with
+// quarter-unit workgroups (float64 colour at 5 / 6 / 8 waves: 0.426 / 0.428 / 0.414 ms per 32-frame launch; the IEEE-
+// division float64 kernel needs more registers and runs at 5).  Measured and settled (DESIGN.md §4): lanes whose voxel
+// projects outside the image issue no depth gather (0.415-0.421 -> 0.409-0.412 ms); slices with no update in the
+// batch are not written back (-1.5 %).
+constexpr int INT_WAVES_PER_EU = 8;
+// Reciprocal table: y[n] = RN(1/n) for n in [1, RCP_N].  For b = w + 1 an integer in that range, q0 = RN(a*y),
+// r = fma(-b, q0, a) (exact), q = RN(q0 + r*y) is RN(a/b) -- Markstein's theorem (y correctly rounded, q0 within one
+// ulp, no underflow in r; binary32 and binary64 alike): the IEEE quotient bit for bit with 3 operations and an LDS
+// load instead of the ~10-instruction division sequence.  The host takes this kernel (FAST) only while every weight
+// is an integer count of updates below RCP_N (frames since reset + the batch < RCP_N) and the state comes from
+// integration alone (no imported units): then |a| is 0 or far above the underflow range (tsdf: a sum of a running
+// mean and a term quantised by the depth / camera-distance floats; colour: c*w + rgb >= 0 with c a mean of bytes).
+// Otherwise the IEEE divisions (FAST = false: tests/test_gpu_tsdf.py::test_long_scan_crosses_reciprocal_table and
+// ::test_ieee_division_kernel_after_import run both across the switch).
+constexpr int RCP_N = 2048;  // 16 KiB (float64) / 8 KiB (float32) of LDS per workgroup: 8 quarter-unit workgroups per CU
+
+// Phases A and B of one frame for a lane's ZB voxels at column position (px, py, pz), slice start z0: the certified
+// projections and the (depth, colour) gathers.  No voxel state is read, so the fine slices' frame pipeline issues them
+// ahead of earlier frames' updates (integrate_item).
 template <int ZB>
 __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateParams& p, int npx, float px, float py,
                                           float pz, int z0, int (&pixv)[ZB], float (&pcz)[ZB], float (&dv)[ZB],
@@ -795,9 +812,13 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
         pc[1] += es1;
         pc[2] += es2;
     }
+    // phase A: projections of the ZB voxels
 #pragma unroll
     for (int k = 0; k < ZB; ++k) {
         const float nu = pc[0] * p.fx, nv = pc[1] * p.fy;
+        // Certified fast projection.  Only floor(u), floor(v) and the bound tests are used, so u = nu * rcp(z) decides
+        // them exactly unless u lies within proj_eps of an integer (the bound tests 0.0001 and W - 0.0001 sit 1e-4
+        // from integers); those rare waves redo the IEEE quotients.
         const float rz = __builtin_amdgcn_rcpf(pc[2]);
         float u_f = (nu * rz + p.cx) + 0.5f;
         float v_f = (nv * rz + p.cy) + 0.5f;
@@ -807,6 +828,7 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
             u_f = ((nu / pc[2]) + p.cx) + 0.5f;
             v_f = ((nv / pc[2]) + p.cy) + 0.5f;
         }
+        // non-short-circuit test keeps all ZB projections in one basic block
         const bool ok = (pc[2] > 0.0f) & (u_f >= 0.0001f) & (u_f < p.safe_w) & (v_f >= 0.0001f) & (v_f < p.safe_h);
         pixv[k] = ok ? (int)__umul24((unsigned)(int)v_f, (unsigned)p.W) + (int)u_f : -1;
         pcz[k] = pc[2];
@@ -814,11 +836,13 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
         pc[1] += es1;
         pc[2] += es2;
     }
+    // phase B: every gather issued before any use (buffer loads: wave-uniform resource + 32-bit byte offset, no per-lane
+    // 64-bit address math)
 #pragma unroll
     for (int k = 0; k < ZB; ++k) {
         dv[k] = 0.0f;
         cv[k] = 0u;
-        if (pixv[k] >= 0) {
+        if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
             const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, pixv[k] * 8, 0, 0);
             dv[k] = __uint_as_float(raw.x);
             cv[k] = raw.y;
@@ -826,22 +850,262 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
     }
 }
 
-// Occupancy: the integrate lives on it (DESIGN.md §4): 64 VGPRs, 8 waves per SIMD for both colour precisions with
-// quarter-unit workgroups (float64 colour at 5 / 6 / 8 waves: 0.426 / 0.428 / 0.414 ms per 32-frame launch; the IEEE-
-// division float64 kernel needs more registers and runs at 5).  Measured and settled (DESIGN.md §4): lanes whose voxel
-// projects outside the image issue no depth gather (0.415-0.421 -> 0.409-0.412 ms); slices with no update in the
-// batch are not written back (-1.5 %).
-constexpr int INT_WAVES_PER_EU = 8;
-// Reciprocal table: y[n] = RN(1/n) for n in [1, RCP_N].  For b = w + 1 an integer in that range, q0 = RN(a*y),
-// r = fma(-b, q0, a) (exact), q = RN(q0 + r*y) is RN(a/b) -- Markstein's theorem (y correctly rounded, q0 within one
-// ulp, no underflow in r; binary32 and binary64 alike): the IEEE quotient bit for bit with 3 operations and an LDS
-// load instead of the ~10-instruction division sequence.  The host takes this kernel (FAST) only while every weight
-// is an integer count of updates below RCP_N (frames since reset + the batch < RCP_N) and the state comes from
-// integration alone (no imported units): then |a| is 0 or far above the underflow range (tsdf: a sum of a running
-// mean and a term quantised by the depth / camera-distance floats; colour: c*w + rgb >= 0 with c a mean of bytes).
-// Otherwise the IEEE divisions (FAST = false: tests/test_gpu_tsdf.py::test_long_scan_crosses_reciprocal_table and
-// ::test_ieee_division_kernel_after_import run both across the switch).
-constexpr int RCP_N = 2048;  // 16 KiB (float64) / 8 KiB (float32) of LDS per workgroup: 8 quarter-unit workgroups per CU
+// Phase C of one frame, state-independent too: the candidate test on df = d - z.  The ray multiplier (the volume's one
+// table, not a per-frame copy) is gathered only by the candidate lanes: it is >= 1 and rounding is monotone, so
+// (d - z) * m > -trunc implies d - z > -trunc; the update's test on the product is then Open3D's.  mv: the gathered
+// multiplier's float bits on the candidate lanes.  On the other lanes it is not a multiplier -- SHARE (the coarse loop):
+// the gather's byte offset, offset and result in one register, which the 64-VGPR float64-colour kernel needs; !SHARE
+// (the fine pipeline's slots, 3-4 % faster per launch so): zero -- so df * mv may be anything there, NaN included;
+// cand is false on those lanes and voxel_update only selects.  Use mv or the product outside a select on cand nowhere.
+template <int ZB, bool SHARE>
+__device__ __forceinline__ void frame_candidates(const IntegrateParams& p, int npx, const int (&pixv)[ZB],
+                                                 const float (&pcz)[ZB], const float (&dv)[ZB], bool (&cand)[ZB],
+                                                 float (&df)[ZB], unsigned (&mv)[ZB]) {
+    const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
+#pragma unroll
+    for (int k = 0; k < ZB; ++k) {
+        df[k] = dv[k] - pcz[k];
+        cand[k] = (pixv[k] >= 0) & (dv[k] > 0.0f) & (df[k] > -p.trunc);
+        if constexpr (SHARE) {
+            mv[k] = (unsigned)pixv[k] * 4u;
+            if (cand[k]) mv[k] = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, (int)mv[k], 0, 0);
+        } else {
+            mv[k] = 0u;
+            if (cand[k]) mv[k] = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, pixv[k] * 4, 0, 0);
+        }
+    }
+}
+
+// Phase D for one voxel and one frame: the update of a candidate lane whose scaled distance sdf = (d - z) * m passes
+// Open3D's test, in select form (identical values, no exec-mask branches).  c: the frame's packed colour at the pixel.
+// The order of the floating-point operations is Open3D's, bit for bit (no contraction; the explicit fma calls are
+// Markstein's correction).
+template <bool C64, bool FAST, typename CT>
+__device__ __forceinline__ void voxel_update(bool cand, float sdf, uint32_t c, bool use_color, const IntegrateParams& p,
+                                             const float* s_r32, const double* s_r64, float& ts, float& wt, CT& cr,
+                                             CT& cg, CT& cb, unsigned& upd) {
+    const bool doit = cand & (sdf > -p.trunc);
+    const float sv = sdf * p.trunc_inv;
+    const float tn = (sv < 1.0f) ? sv : 1.0f;
+    const float wv = wt;
+    const float w1 = wv + 1.0f;
+    const float ta = ts * wv + tn;
+    float tsn;  // (tsdf * w + t) / (w + 1): the IEEE quotient, tsdf bit-exact
+    // one table read per voxel for the tsdf and the colour quotients (round 3: +0.8 %)
+    const double y64 = (FAST && C64) ? s_r64[(int)w1] : 0.0;
+    if constexpr (FAST) {
+        const float y = C64 ? (float)y64 : s_r32[(int)w1];
+        const float q0 = ta * y;
+        tsn = __builtin_fmaf(__builtin_fmaf(-w1, q0, ta), y, q0);
+    } else {
+        tsn = ta / w1;
+    }
+    ts = doit ? tsn : ts;
+    // the colour means, selected by (update & the frame has colour): one select per lane, where a branch on the
+    // wave-uniform use_color around each voxel's select cost the float64-colour frame pipeline 2-9 % per launch
+    const bool docol = doit & use_color;
+    if constexpr (C64) {  // Open3D: color = (color * weight + rgb) / (weight + 1.0f) in float64
+        // every lane, in select form (skipping voxels without an updating lane: slower)
+        const double wd = (double)wv, w1d = (double)w1;
+        const double ar = cr * wd + (double)(c & 0xFFu);
+        const double ag = cg * wd + (double)((c >> 8) & 0xFFu);
+        const double ab = cb * wd + (double)((c >> 16) & 0xFFu);
+        double nr, ng, nb;
+        if constexpr (FAST) {
+            const double y = y64;
+            const double q0r = ar * y, q0g = ag * y, q0b = ab * y;
+            nr = __builtin_fma(__builtin_fma(-w1d, q0r, ar), y, q0r);
+            ng = __builtin_fma(__builtin_fma(-w1d, q0g, ag), y, q0g);
+            nb = __builtin_fma(__builtin_fma(-w1d, q0b, ab), y, q0b);
+        } else {
+            nr = ar / w1d;
+            ng = ag / w1d;
+            nb = ab / w1d;
+        }
+        cr = docol ? nr : cr;
+        cg = docol ? ng : cg;
+        cb = docol ? nb : cb;
+    } else {  // float32 state, one reciprocal for the three channels (|rel| <= 1e-4)
+        const float rw = __builtin_amdgcn_rcpf(w1);
+        const float nr = ((float)cr * wv + (float)(c & 0xFFu)) * rw;
+        const float ng = ((float)cg * wv + (float)((c >> 8) & 0xFFu)) * rw;
+        const float nb = ((float)cb * wv + (float)((c >> 16) & 0xFFu)) * rw;
+        cr = docol ? nr : cr;
+        cg = docol ? ng : cg;
+        cb = docol ? nb : cb;
+    }
+    wt = doit ? w1 : wv;
+    upd += doit ? 1u : 0u;
+}
+
+// The frames of `mask` for a coarse slice: one frame's phases A to D after the other (the unit's other waves hide the
+// gathers' latency).
+template <bool C64, bool FAST, int ZB, typename CT>
+__device__ __forceinline__ void integrate_frames(const BatchFrame* __restrict__ frames, const IntegrateParams& p,
+                                                 int npx, unsigned long long mask, float px, float py, float pz, int z0,
+                                                 const float* s_r32, const double* s_r64, float (&ts)[ZB],
+                                                 float (&wt)[ZB], CT (&cr)[ZB], CT (&cg)[ZB], CT (&cb)[ZB],
+                                                 unsigned& upd) {
+    for (unsigned long long m = mask; m; m &= m - 1) {
+        const int f = __ffsll((long long)m) - 1;
+        const BatchFrame& fr = frames[f];
+        const bool use_color = fr.color != nullptr;
+        // per-frame copies of the voxel column's position: the compiler pairs the rows' products (packed float32 math)
+        // and would otherwise keep px, py, pz duplicated in register pairs across the whole frame loop (8 VGPRs for 3
+        // values: the float64-colour kernel then spills)
+        float fpx = px, fpy = py, fpz = pz;
+        asm volatile("" : "+v"(fpx), "+v"(fpy), "+v"(fpz));
+        int pixv[ZB];
+        float pcz[ZB], dv[ZB], df[ZB];
+        uint32_t cv[ZB];
+        bool cand[ZB];
+        unsigned mv[ZB];
+        frame_tap<ZB>(fr, p, npx, fpx, fpy, fpz, z0, pixv, pcz, dv, cv);
+        frame_candidates<ZB, true>(p, npx, pixv, pcz, dv, cand, df, mv);
+        // updates in frame order
+#pragma unroll
+        for (int k = 0; k < ZB; ++k)
+            voxel_update<C64, FAST>(cand[k], df[k] * __uint_as_float(mv[k]), cv[k], use_color, p, s_r32, s_r64, ts[k],
+                                    wt[k], cr[k], cg[k], cb[k], upd);
+    }
+}
+
+// One work item: slice s (this wave's) of the unit of work entry w -- its ZB voxels per lane loaded (or zero for a
+// fresh unit), taken through the batch's frames of w.mask and written back.  ZB == 2: the fine slices (KT their
+// pipeline's depth).
+template <bool C64, bool FAST, int ZB, int KT>
+__device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ frames, const IntegrateParams& p,
+                                               const TsdfDev& d, const UnitWork& w, int s, int npx,
+                                               const float* s_r32, const double* s_r64, unsigned& upd) {
+    using CT = typename std::conditional<C64, double, float>::type;
+    const int ent = w.id;
+    const unsigned long long mask = w.mask;
+    if (ent == -1) return;
+    const int id = ent & 0x7FFFFFFF;
+    const bool fresh = ent < 0;
+    // the lane's column from a per-item copy of the thread index: the compiler would otherwise hoist lane, lane >> 3 and
+    // lane & 7 out of the item loop and keep them in registers through the frame loop, which has none to spare (the
+    // float64-colour kernels then spill them)
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
+    // wave = 8 x 8 columns: a square patch of the unit's xy plane projects to fewer pixel rows
+    const int x = (s & 2) * 4 + (lane >> 3), y = (s & 1) * 8 + (lane & 7);
+    const int col = x * 16 + y;
+    const int z0 = (s >> 2) * ZB;
+    float* base = d.vox + (size_t)id * (C64 ? UNIT_FLOATS_C64 : UNIT_FLOATS);
+    // colour plane c of voxel vi: float32 planes addressed from base (one address register for the whole record: a
+    // separate colour pointer costs ~34 VGPRs in this kernel), float64 through a buffer resource over the record's
+    // float64 planes
+    const __amdgpu_buffer_rsrc_t col64 = make_rsrc(base + 2 * UNIT_VOX, 3 * UNIT_VOX * 8);
+    float ts[ZB], wt[ZB];
+    CT cr[ZB], cg[ZB], cb[ZB];
+#pragma unroll
+    for (int k = 0; k < ZB; ++k) {
+        const int vi = (z0 + k) * 256 + col;
+        if (fresh) {
+            ts[k] = wt[k] = 0.0f;
+            cr[k] = cg[k] = cb[k] = (CT)0;
+        } else {
+            ts[k] = base[vi];
+            wt[k] = base[UNIT_VOX + vi];
+            if constexpr (C64) {
+                cr[k] = ld_f64(col64, vi);
+                cg[k] = ld_f64(col64, UNIT_VOX + vi);
+                cb[k] = ld_f64(col64, 2 * UNIT_VOX + vi);
+            } else {
+                cr[k] = base[2 * UNIT_VOX + vi];
+                cg[k] = base[3 * UNIT_VOX + vi];
+                cb[k] = base[4 * UNIT_VOX + vi];
+            }
+        }
+    }
+    const float ox = (float)((double)w.kx * p.unit_len);
+    const float oy = (float)((double)w.ky * p.unit_len);
+    const float oz = (float)((double)w.kz * p.unit_len);
+    const float px = (p.half + p.vl * (float)x) + ox;
+    const float py = (p.half + p.vl * (float)y) + oy;
+    const float pz = p.half + oz;
+    unsigned iu = 0;  // this item's updates
+    if constexpr (ZB == 2) {
+        // Frame pipeline (the fine slices serve batches with few units, whose waves cannot hide a frame's dependent
+        // gathers behind other waves: the wave's chain of frames IS the batch's time).  Every load of a frame is
+        // state-independent -- the projections and (depth, colour) gathers (frame_tap), the candidate test and the
+        // multiplier gather (frame_candidates) -- only the update (voxel_update) waits for it and reads the voxel
+        // state.  So frame f+KT's tap and frame f+KC's candidate stage are issued before frame f's update, from
+        // KT + 1 register slots (the loop is unrolled over the slots so every slot is a fixed register set: a
+        // rotating copy would wait for the loads in flight).  The updates still run in frame order with the same
+        // arithmetic: the bits are the unpipelined loop's.  KT = 1, KC = 0 is the round-5 one-frame skew.
+        // The pipeline stands here, not in a function of its own as the coarse loop does: with the voxel state passed
+        // by reference the float64-colour kernels took 6 more VGPRs and the fused fine launch ran 5 % slower.
+        constexpr int KC = KT - 1, RS = KT + 1;
+        unsigned long long mt = mask;  // frames not yet tapped
+        int fs[RS];                     // frame of each slot (wave-uniform), -1: past the last frame
+        int pixv[RS][ZB];
+        float pcz[RS][ZB], dv[RS][ZB], df[RS][ZB];
+        uint32_t cv[RS][ZB];
+        bool cand[RS][ZB];
+        unsigned mv[RS][ZB];
+        auto tap = [&](auto J) __attribute__((always_inline)) {
+            constexpr int j = decltype(J)::value;
+            if (mt) {
+                const int f = __ffsll((long long)mt) - 1;
+                mt &= mt - 1;
+                fs[j] = f;
+                frame_tap<ZB>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
+            } else {
+                fs[j] = -1;
+            }
+        };
+        auto stage_c = [&](auto J) __attribute__((always_inline)) {
+            constexpr int j = decltype(J)::value;
+            if (fs[j] < 0) return;
+            frame_candidates<ZB, false>(p, npx, pixv[j], pcz[j], dv[j], cand[j], df[j], mv[j]);
+        };
+        auto stage_d = [&](auto J) __attribute__((always_inline)) -> bool {
+            constexpr int j = decltype(J)::value;
+            if (fs[j] < 0) return false;
+            const bool use_color = frames[fs[j]].color != nullptr;
+#pragma unroll
+            for (int k = 0; k < ZB; ++k)
+                voxel_update<C64, FAST>(cand[j][k], df[j][k] * __uint_as_float(mv[j][k]), cv[j][k], use_color, p, s_r32,
+                                        s_r64, ts[k], wt[k], cr[k], cg[k], cb[k], iu);
+            return true;
+        };
+        // one iteration = frame f in slot J: the candidate stage of f + KC, the tap of f + KT (into the slot frame f - 1
+        // left), the update of f
+        auto iter = [&](auto J) __attribute__((always_inline)) -> bool {
+            constexpr int j = decltype(J)::value;
+            stage_c(std::integral_constant<int, (j + KC) % RS>{});
+            tap(std::integral_constant<int, (j + KT) % RS>{});
+            return stage_d(J);
+        };
+        // prologue: taps of the first KT frames, candidate stages of the first KC
+        static_for<KT>(tap);
+        static_for<KC>(stage_c);
+        while (static_all<RS>(iter)) {
+        }
+    } else
+        integrate_frames<C64, FAST, ZB>(frames, p, npx, mask, px, py, pz, z0, s_r32, s_r64, ts, wt, cr, cg, cb, iu);
+    upd += iu;
+    // a slice none of whose voxels updated in this batch still holds its HBM values (fresh ones: zeros)
+    if (!fresh && !__any(iu != 0u)) return;
+#pragma unroll
+    for (int k = 0; k < ZB; ++k) {
+        const int vi = (z0 + k) * 256 + col;
+        base[vi] = ts[k];
+        base[UNIT_VOX + vi] = wt[k];
+        if constexpr (C64) {
+            st_f64(col64, vi, cr[k]);
+            st_f64(col64, UNIT_VOX + vi, cg[k]);
+            st_f64(col64, 2 * UNIT_VOX + vi, cb[k]);
+        } else {
+            base[2 * UNIT_VOX + vi] = cr[k];
+            base[3 * UNIT_VOX + vi] = cg[k];
+            base[4 * UNIT_VOX + vi] = cb[k];
+        }
+    }
+}
 
 // One workgroup of INT_WG waves per unit part (a quarter unit by default: small workgroups let the CU keep 6-8 of them
 // resident instead of one 16-wave unit -- a unit-sized workgroup left the float64-colour kernel at 4 waves per SIMD
@@ -856,20 +1120,26 @@ struct RcpLds {
     float r32[(FAST && !C64) ? RCP_N + 1 : 1];
     double r64[(FAST && C64) ? RCP_N + 1 : 1];
 };
-// the integrate of a batch as workgroup `bid` of `nblk` (k_batch_integrate; the integrate half of k_integrate_touch)
-template <bool C64, bool FAST, int ZB, int KT>
+// The integrate of a batch as workgroup `bid` of `nblk`: the one text behind k_batch_integrate (the product kernel) and
+// the integrate half of k_integrate_touch / k_integrate_touch_fine.  Everything per item is shared (integrate_item: the
+// record's load and store, the frame loops, the tap, the candidate stage, the per-voxel update, each written once
+// above); the callers differ in three things only, all passed in: the workgroup's id and count (blockIdx.x /
+// gridDim.x against the fused launch's split of the grid), the home of the reciprocal table (s_r32 / s_r64: static
+// __shared__ arrays against a member of the fused kernels' LDS union) and the work-list index (HEAVY: the fused
+// launch walks heavy units first, the rest back to front -- k_batch_units).
+// Decision and measurements: DESIGN.md §4.2.
+//
+// work item = (unit, part): the PARTS parts of a unit are items 8 apart, so they run on one XCD (blocks are dealt
+// round-robin over the 8 XCDs) at about the same time and share its L2's copy of the footprint.
+// The grid is sized for large batches (8x the resident workgroups): a workgroup without an item leaves before
+// building the reciprocal table -- for a batch of few units (a spatial shard) the idle workgroups' tables had cost
+// more than the integrate itself (r05e: a 1/8 shard's 64-frame batch 165-200 us whatever its slicing)
+template <bool C64, bool FAST, int ZB, int KT, bool HEAVY>
 __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ frames, const IntegrateParams& p,
                                                const TsdfDev& d, const UnitWork* __restrict__ work,
-                                               const int* __restrict__ wcount, RcpLds<C64, FAST>& R, int bid, int nblk) {
-    using CT = typename std::conditional<C64, double, float>::type;
+                                               const int* __restrict__ wcount, float* s_r32, double* s_r64, int bid,
+                                               int nblk) {
     constexpr int PARTS = 4 * (UNIT_RES / ZB) / INT_WG;  // workgroups per unit (INT_PARTS at the default ZB)
-    float* s_r32 = R.r32;
-    double* s_r64 = R.r64;
-    // work item = (unit, part): the PARTS parts of a unit are items 8 apart, so they run on one XCD (blocks are dealt
-    // round-robin over the 8 XCDs) at about the same time and share its L2's copy of the footprint.
-    // The grid is sized for large batches (8x the resident workgroups): a workgroup without an item leaves before
-    // building the reciprocal table -- for a batch of few units (a spatial shard) the idle workgroups' tables had cost
-    // more than the integrate itself (r05e: a 1/8 shard's 64-frame batch 165-200 us whatever its slicing)
     {
         const int n0 = __builtin_amdgcn_readfirstlane(__hip_atomic_load(wcount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         if (bid >= (PARTS == 1 ? n0 : ((n0 + 7) / 8) * 8 * PARTS)) return;
@@ -881,714 +1151,32 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
         }
         __syncthreads();
     }
-    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // once, in a scalar register
     const int n = *wcount;
-    const int nh = wcount[2];  // heavy units first; the rest are stored back to front (k_batch_units)
+    const int nh = HEAVY ? wcount[2] : 0;  // heavy units first; the rest are stored back to front (k_batch_units)
     const int npx = p.W * p.H;
     unsigned upd = 0;  // per lane: <= ZB voxels x 64 frames x units per workgroup, far below 2^32
-    {
-        const int b = bid;
-        const int items = PARTS == 1 ? n : ((n + 7) / 8) * 8 * PARTS;
-        for (int it = b; it < items; it += nblk) {
-            const int u = PARTS == 1 ? it : (it / (8 * PARTS)) * 8 + (it & 7);
-            if (PARTS > 1 && u >= n) continue;
-            const int part = PARTS == 1 ? 0 : (it >> 3) % PARTS;
-            const int s = __builtin_amdgcn_readfirstlane(part * INT_WG + (int)(threadIdx.x >> 6));  // slice of this wave
-            const UnitWork& w = work[u < nh ? u : n - 1 - (u - nh)];
-            const int ent = w.id;
-            const unsigned long long mask = w.mask;
-            if (ent != -1) {
-                const int id = ent & 0x7FFFFFFF;
-                const bool fresh = ent < 0;
-                // wave = 8 x 8 columns: a square patch of the unit's xy plane projects to fewer pixel rows
-                const int x = (s & 2) * 4 + (lane >> 3), y = (s & 1) * 8 + (lane & 7);
-                const int col = x * 16 + y;
-                const int z0 = (s >> 2) * ZB;
-                float* base = d.vox + (size_t)id * (C64 ? UNIT_FLOATS_C64 : UNIT_FLOATS);
-                // colour plane c of voxel vi: float32 planes addressed from base (one address register for the
-                // whole record: a separate colour pointer costs ~34 VGPRs in this kernel), float64 through a buffer
-                // resource over the record's float64 planes
-                const __amdgpu_buffer_rsrc_t col64 = make_rsrc(base + 2 * UNIT_VOX, 3 * UNIT_VOX * 8);
-                float ts[ZB], wt[ZB];
-                CT cr[ZB], cg[ZB], cb[ZB];
-#pragma unroll
-                for (int k = 0; k < ZB; ++k) {
-                    const int vi = (z0 + k) * 256 + col;
-                    if (fresh) {
-                        ts[k] = wt[k] = 0.0f;
-                        cr[k] = cg[k] = cb[k] = (CT)0;
-                    } else {
-                        ts[k] = base[vi];
-                        wt[k] = base[UNIT_VOX + vi];
-                        if constexpr (C64) {
-                            cr[k] = ld_f64(col64, vi);
-                            cg[k] = ld_f64(col64, UNIT_VOX + vi);
-                            cb[k] = ld_f64(col64, 2 * UNIT_VOX + vi);
-                        } else {
-                            cr[k] = base[2 * UNIT_VOX + vi];
-                            cg[k] = base[3 * UNIT_VOX + vi];
-                            cb[k] = base[4 * UNIT_VOX + vi];
-                        }
-                    }
-                }
-                const float ox = (float)((double)w.kx * p.unit_len);
-                const float oy = (float)((double)w.ky * p.unit_len);
-                const float oz = (float)((double)w.kz * p.unit_len);
-                const float px = (p.half + p.vl * (float)x) + ox;
-                const float py = (p.half + p.vl * (float)y) + oy;
-                const float pz = p.half + oz;
-                const unsigned upd0 = upd;
-                if constexpr (ZB == 2) {
-                    // Frame pipeline (the fine slices serve batches with few units, whose waves cannot hide a frame's
-                    // dependent gathers behind other waves: the wave's chain of frames IS the batch's time).  Every
-                    // load of a frame is state-independent -- the projections and (depth, colour) gathers (tap), the
-                    // candidate test on d - z and the multiplier gather (stage C) -- only the update test on the scaled
-                    // distance, the clamped term and the running means (stage D) wait for it and read the voxel state.
-                    // So frame f+KT's tap and frame f+KC's stage C are issued before frame f's update,
-                    // from KT + 1 register slots (the loop is unrolled over the slots so every slot is a fixed
-                    // register set: a rotating copy would wait for the loads in flight).  The updates still run in
-                    // frame order with the same arithmetic: the bits are the unpipelined loop's.  KT = 1, KC = 0 is the
-                    // round-5 one-frame skew.
-                    constexpr int KC = KT - 1, RS = KT + 1;
-                    unsigned long long mt = mask;  // frames not yet tapped
-                    int fs[RS];                     // frame of each slot (wave-uniform), -1: past the last frame
-                    int pixv[RS][ZB];
-                    float pcz[RS][ZB], dv[RS][ZB], mv[RS][ZB], dfv[RS][ZB];
-                    uint32_t cv[RS][ZB];
-                    bool cav[RS][ZB];
-                    auto tap = [&](auto J) __attribute__((always_inline)) {
-                        constexpr int j = decltype(J)::value;
-                        if (mt) {
-                            const int f = __ffsll((long long)mt) - 1;
-                            mt &= mt - 1;
-                            fs[j] = f;
-                            frame_tap<ZB>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
-                        } else {
-                            fs[j] = -1;
-                        }
-                    };
-                    auto stage_c = [&](auto J) __attribute__((always_inline)) {
-                        constexpr int j = decltype(J)::value;
-                        if (fs[j] < 0) return;
-                        // candidates: the multiplier is >= 1, so (d - z) * m > -trunc implies d - z > -trunc -- only
-                        // these lanes gather it, from the volume's one table (stage D makes the update test itself)
-                        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            dfv[j][k] = dv[j][k] - pcz[j][k];
-                            cav[j][k] = (pixv[j][k] >= 0) & (dv[j][k] > 0.0f) & (dfv[j][k] > -p.trunc);
-                            mv[j][k] = 0.0f;
-                            if (cav[j][k])
-                                mv[j][k] = __uint_as_float(
-                                    __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, pixv[j][k] * 4, 0, 0));
-                        }
-                    };
-                    auto stage_d = [&](auto J) __attribute__((always_inline)) -> bool {
-                        constexpr int j = decltype(J)::value;
-                        if (fs[j] < 0) return false;
-                        const bool use_color = frames[fs[j]].color != nullptr;
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            const float sdf = dfv[j][k] * mv[j][k];
-                            const bool doit = cav[j][k] & (sdf > -p.trunc);
-                            const float sv = sdf * p.trunc_inv;
-                            const float tn = (sv < 1.0f) ? sv : 1.0f;
-                            const float wv = wt[k];
-                            const float w1 = wv + 1.0f;
-                            const float ta = ts[k] * wv + tn;
-                            float tsn;
-                            const double y64 = (FAST && C64) ? s_r64[(int)w1] : 0.0;
-                            if constexpr (FAST) {
-                                const float y = C64 ? (float)y64 : s_r32[(int)w1];
-                                const float q0 = ta * y;
-                                tsn = __builtin_fmaf(__builtin_fmaf(-w1, q0, ta), y, q0);
-                            } else {
-                                tsn = ta / w1;
-                            }
-                            ts[k] = doit ? tsn : ts[k];
-                            if (use_color) {
-                                const uint32_t c = cv[j][k];
-                                if constexpr (C64) {
-                                    const double wd = (double)wv, w1d = (double)w1;
-                                    const double ar = cr[k] * wd + (double)(c & 0xFFu);
-                                    const double ag = cg[k] * wd + (double)((c >> 8) & 0xFFu);
-                                    const double ab = cb[k] * wd + (double)((c >> 16) & 0xFFu);
-                                    double nr, ng, nb;
-                                    if constexpr (FAST) {
-                                        const double y = y64;
-                                        const double q0r = ar * y, q0g = ag * y, q0b = ab * y;
-                                        nr = __builtin_fma(__builtin_fma(-w1d, q0r, ar), y, q0r);
-                                        ng = __builtin_fma(__builtin_fma(-w1d, q0g, ag), y, q0g);
-                                        nb = __builtin_fma(__builtin_fma(-w1d, q0b, ab), y, q0b);
-                                    } else {
-                                        nr = ar / w1d;
-                                        ng = ag / w1d;
-                                        nb = ab / w1d;
-                                    }
-                                    cr[k] = doit ? nr : cr[k];
-                                    cg[k] = doit ? ng : cg[k];
-                                    cb[k] = doit ? nb : cb[k];
-                                } else {
-                                    const float rw = __builtin_amdgcn_rcpf(w1);
-                                    const float nr = ((float)cr[k] * wv + (float)(c & 0xFFu)) * rw;
-                                    const float ng = ((float)cg[k] * wv + (float)((c >> 8) & 0xFFu)) * rw;
-                                    const float nb = ((float)cb[k] * wv + (float)((c >> 16) & 0xFFu)) * rw;
-                                    cr[k] = doit ? nr : cr[k];
-                                    cg[k] = doit ? ng : cg[k];
-                                    cb[k] = doit ? nb : cb[k];
-                                }
-                            }
-                            wt[k] = doit ? w1 : wv;
-                            upd += doit ? 1u : 0u;
-                        }
-                        return true;
-                    };
-                    // one iteration = frame f in slot J: stage C of f + KC, the tap of f + KT (into the slot frame f - 1
-                    // left), the update of f
-                    auto iter = [&](auto J) __attribute__((always_inline)) -> bool {
-                        constexpr int j = decltype(J)::value;
-                        stage_c(std::integral_constant<int, (j + KC) % RS>{});
-                        tap(std::integral_constant<int, (j + KT) % RS>{});
-                        return stage_d(J);
-                    };
-                    // prologue: taps of the first KT frames, stage C of the first KC
-                    static_for<KT>(tap);
-                    static_for<KC>(stage_c);
-                    while (static_all<RS>(iter)) {
-                    }
-                } else {
-                    for (unsigned long long m = mask; m; m &= m - 1) {
-                        const int f = __ffsll((long long)m) - 1;
-                        const BatchFrame& fr = frames[f];
-                        const __amdgpu_buffer_rsrc_t dc_rsrc = make_rsrc(fr.dc, npx * 8);
-                        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
-                        const bool use_color = fr.color != nullptr;
-                        float pc[3];
-                        // per-frame copies of the voxel column's position: the compiler pairs the rows' products
-                        // (packed float32 math) and would otherwise keep px, py, pz duplicated in register pairs across
-                        // the whole frame loop (8 VGPRs for 3 values: the float64-colour kernel then spills)
-                        float fpx = px, fpy = py, fpz = pz;
-                        asm volatile("" : "+v"(fpx), "+v"(fpy), "+v"(fpz));
-#pragma unroll
-                        for (int r = 0; r < 3; ++r) {
-                            const float a = fr.E[r * 4 + 0] * fpx;
-                            const float b = fr.E[r * 4 + 1] * fpy;
-                            const float c = fr.E[r * 4 + 2] * fpz;
-                            pc[r] = ((a + b) + c) + fr.E[r * 4 + 3];
-                        }
-                        const float es0 = fr.es[0], es1 = fr.es[1], es2 = fr.es[2];
-                        for (int k = 0; k < z0; ++k) {  // wave-uniform: advance to this slice's first voxel
-                            pc[0] += es0;
-                            pc[1] += es1;
-                            pc[2] += es2;
-                        }
-                        // phase A: projections of the ZB voxels
-                        int pixv[ZB];
-                        float pcz[ZB];
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            const float nu = pc[0] * p.fx, nv = pc[1] * p.fy;
-                            // Certified fast projection.  Only floor(u), floor(v) and the bound tests are used, so
-                            // u = nu * rcp(z) decides them exactly unless u lies within proj_eps of an integer (the
-                            // bound tests 0.0001 and W - 0.0001 sit 1e-4 from integers); those rare waves redo the
-                            // IEEE quotients.
-                            const float rz = __builtin_amdgcn_rcpf(pc[2]);
-                            float u_f = (nu * rz + p.cx) + 0.5f;
-                            float v_f = (nv * rz + p.cy) + 0.5f;
-                            const bool sure = !(pc[2] > 0.0f) ||
-                                              ((int)(fabsf(u_f - __builtin_rintf(u_f)) > p.proj_eps) &
-                                               (int)(fabsf(v_f - __builtin_rintf(v_f)) > p.proj_eps));
-                            if (!sure) {
-                                u_f = ((nu / pc[2]) + p.cx) + 0.5f;
-                                v_f = ((nv / pc[2]) + p.cy) + 0.5f;
-                            }
-                            // non-short-circuit test keeps all ZB projections in one basic block
-                            const bool ok = (pc[2] > 0.0f) & (u_f >= 0.0001f) & (u_f < p.safe_w) & (v_f >= 0.0001f) &
-                                            (v_f < p.safe_h);
-                            pixv[k] = ok ? (int)__umul24((unsigned)(int)v_f, (unsigned)p.W) + (int)u_f : -1;
-                            pcz[k] = pc[2];
-                            pc[0] += es0;
-                            pc[1] += es1;
-                            pc[2] += es2;
-                        }
-                        // phase B: every depth gather issued before any use (buffer loads: wave-uniform resource +
-                        // 32-bit byte offset, no per-lane 64-bit address math)
-                        float dv[ZB];
-                        uint32_t cv[ZB];
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            dv[k] = 0.0f;
-                            cv[k] = 0u;
-                            if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
-                                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, pixv[k] * 8, 0, 0);
-                                dv[k] = __uint_as_float(raw.x);
-                                cv[k] = raw.y;
-                            }
-                        }
-                        // phase C: the depth test.  The ray multiplier (the volume's one table, not a per-frame copy)
-                        // is gathered only by the candidate lanes: it is >= 1 and rounding is monotone, so
-                        // (d - z) * m > -trunc implies d - z > -trunc; the test on the product is then Open3D's
-                        bool doitv[ZB];
-                        float sdfv[ZB];
-                        unsigned mv[ZB];  // the gather's byte offset, then its result in the same register (the other
-                                          // lanes keep the offset: their product is never selected)
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            sdfv[k] = dv[k] - pcz[k];
-                            doitv[k] = (pixv[k] >= 0) & (dv[k] > 0.0f) & (sdfv[k] > -p.trunc);
-                            mv[k] = (unsigned)pixv[k] * 4u;
-                            if (doitv[k]) mv[k] = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, (int)mv[k], 0, 0);
-                        }
-                        // phase D: updates in frame order (select form: identical values, no exec-mask branches)
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            const float sdf = sdfv[k] * __uint_as_float(mv[k]);
-                            const bool doit = doitv[k] & (sdf > -p.trunc);
-                            const float sv = sdf * p.trunc_inv;
-                            const float tn = (sv < 1.0f) ? sv : 1.0f;
-                            const float wv = wt[k];
-                            const float w1 = wv + 1.0f;
-                            const float ta = ts[k] * wv + tn;
-                            float tsn;  // (tsdf * w + t) / (w + 1): the IEEE quotient, tsdf bit-exact
-                            // one table read per voxel for the tsdf and the colour quotients (round 3: +0.8 %)
-                            const double y64 = (FAST && C64) ? s_r64[(int)w1] : 0.0;
-                            if constexpr (FAST) {
-                                const float y = C64 ? (float)y64 : s_r32[(int)w1];
-                                const float q0 = ta * y;
-                                tsn = __builtin_fmaf(__builtin_fmaf(-w1, q0, ta), y, q0);
-                            } else {
-                                tsn = ta / w1;
-                            }
-                            ts[k] = doit ? tsn : ts[k];
-                            if (use_color) {
-                                if constexpr (C64) {  // Open3D: color = (color * weight + rgb) / (weight + 1.0f) in float64
-                                    {  // every lane, in select form (skipping voxels without an updating lane: slower)
-                                        const double wd = (double)wv, w1d = (double)w1;
-                                        const double ar = cr[k] * wd + (double)(cv[k] & 0xFFu);
-                                        const double ag = cg[k] * wd + (double)((cv[k] >> 8) & 0xFFu);
-                                        const double ab = cb[k] * wd + (double)((cv[k] >> 16) & 0xFFu);
-                                        double nr, ng, nb;
-                                        if constexpr (FAST) {
-                                            const double y = y64;
-                                            const double q0r = ar * y, q0g = ag * y, q0b = ab * y;
-                                            nr = __builtin_fma(__builtin_fma(-w1d, q0r, ar), y, q0r);
-                                            ng = __builtin_fma(__builtin_fma(-w1d, q0g, ag), y, q0g);
-                                            nb = __builtin_fma(__builtin_fma(-w1d, q0b, ab), y, q0b);
-                                        } else {
-                                            nr = ar / w1d;
-                                            ng = ag / w1d;
-                                            nb = ab / w1d;
-                                        }
-                                        cr[k] = doit ? nr : cr[k];
-                                        cg[k] = doit ? ng : cg[k];
-                                        cb[k] = doit ? nb : cb[k];
-                                    }
-                                } else {  // float32 state, one reciprocal for the three channels (|rel| <= 1e-4)
-                                    const float rw = __builtin_amdgcn_rcpf(w1);
-                                    const float nr = ((float)cr[k] * wv + (float)(cv[k] & 0xFFu)) * rw;
-                                    const float ng = ((float)cg[k] * wv + (float)((cv[k] >> 8) & 0xFFu)) * rw;
-                                    const float nb = ((float)cb[k] * wv + (float)((cv[k] >> 16) & 0xFFu)) * rw;
-                                    cr[k] = doit ? nr : cr[k];
-                                    cg[k] = doit ? ng : cg[k];
-                                    cb[k] = doit ? nb : cb[k];
-                                }
-                            }
-                            wt[k] = doit ? w1 : wv;
-                            upd += doit ? 1u : 0u;
-                        }
-                    }
-                }
-                // a slice none of whose voxels updated in this batch still holds its HBM values (fresh ones: zeros)
-                if (!fresh && !__any(upd != upd0)) continue;
-#pragma unroll
-                for (int k = 0; k < ZB; ++k) {
-                    const int vi = (z0 + k) * 256 + col;
-                    base[vi] = ts[k];
-                    base[UNIT_VOX + vi] = wt[k];
-                    if constexpr (C64) {
-                        st_f64(col64, vi, cr[k]);
-                        st_f64(col64, UNIT_VOX + vi, cg[k]);
-                        st_f64(col64, 2 * UNIT_VOX + vi, cb[k]);
-                    } else {
-                        base[2 * UNIT_VOX + vi] = cr[k];
-                        base[3 * UNIT_VOX + vi] = cg[k];
-                        base[4 * UNIT_VOX + vi] = cb[k];
-                    }
-                }
-            }
-        }
+    const int items = PARTS == 1 ? n : ((n + 7) / 8) * 8 * PARTS;
+    for (int it = bid; it < items; it += nblk) {
+        const int u = PARTS == 1 ? it : (it / (8 * PARTS)) * 8 + (it & 7);
+        if (PARTS > 1 && u >= n) continue;
+        const int part = PARTS == 1 ? 0 : (it >> 3) % PARTS;
+        const int s = part * INT_WG + wave;  // slice of this wave
+        integrate_item<C64, FAST, ZB, KT>(frames, p, d, work[!HEAVY || u < nh ? u : n - 1 - (u - nh)], s, npx, s_r32,
+                                          s_r64, upd);
     }
     const unsigned long long tot = wave_sum((unsigned long long)upd);
-    if (lane == 0 && tot) atomicAdd(&d.stats[S_UPDATES], tot);
+    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(&d.stats[S_UPDATES], tot);
 }
 
-// The product kernel keeps its own text (the same per-voxel code as integrate_body): compiled from the shared inlined
-// body, its frame loop gained five uniform branches and lost 1.3 % (0.726 vs 0.717 ms per launch, r06n vs r06j)
+// the integrate of a batch as a launch of its own (the product kernel: <C64, FAST, BZ, 1>; ZB == 2: fine slices)
 template <bool C64, bool FAST, int ZB = BZ, int KT = 1>
 __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : INT_WAVES_PER_EU)) void k_batch_integrate(
     const BatchFrame* __restrict__ frames, IntegrateParams p, TsdfDev d, const UnitWork* __restrict__ work,
     const int* __restrict__ wcount) {
-    using CT = typename std::conditional<C64, double, float>::type;
-    constexpr int PARTS = 4 * (UNIT_RES / ZB) / INT_WG;  // workgroups per unit (INT_PARTS at the default ZB)
-    // one table per kernel: float64 reciprocals for the float64-colour kernel (its float32 ones are their roundings:
-    // (float)RN64(1/n) == RN32(1/n) for every n <= 2^20, no double-rounding case -- tools/markstein_check.cpp),
-    // float32 ones otherwise
     __shared__ float s_r32[(FAST && !C64) ? RCP_N + 1 : 1];
     __shared__ double s_r64[(FAST && C64) ? RCP_N + 1 : 1];
-    // work item = (unit, part): the PARTS parts of a unit are items 8 apart, so they run on one XCD (blocks are dealt
-    // round-robin over the 8 XCDs) at about the same time and share its L2's copy of the footprint.
-    // The grid is sized for large batches (8x the resident workgroups): a workgroup without an item leaves before
-    // building the reciprocal table -- for a batch of few units (a spatial shard) the idle workgroups' tables had cost
-    // more than the integrate itself (r05e: a 1/8 shard's 64-frame batch 165-200 us whatever its slicing)
-    {
-        const int n0 = __builtin_amdgcn_readfirstlane(__hip_atomic_load(wcount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if ((int)blockIdx.x >= (PARTS == 1 ? n0 : ((n0 + 7) / 8) * 8 * PARTS)) return;
-    }
-    if constexpr (FAST) {
-        for (int r = 1 + threadIdx.x; r <= p.rcp_hi; r += 64 * INT_WG) {  // entries 1 .. the batch's largest weight + 1
-            if constexpr (C64) s_r64[r] = 1.0 / (double)r;  // IEEE (correctly rounded) quotients
-            else s_r32[r] = 1.0f / (float)r;
-        }
-        __syncthreads();
-    }
-    const int lane = threadIdx.x & 63;
-    const int n = *wcount;
-    const int npx = p.W * p.H;
-    unsigned upd = 0;  // per lane: <= ZB voxels x 64 frames x units per workgroup, far below 2^32
-    {
-        const int b = blockIdx.x;
-        const int items = PARTS == 1 ? n : ((n + 7) / 8) * 8 * PARTS;
-        for (int it = b; it < items; it += gridDim.x) {
-            const int u = PARTS == 1 ? it : (it / (8 * PARTS)) * 8 + (it & 7);
-            if (PARTS > 1 && u >= n) continue;
-            const int part = PARTS == 1 ? 0 : (it >> 3) % PARTS;
-            const int s = __builtin_amdgcn_readfirstlane(part * INT_WG + (int)(threadIdx.x >> 6));  // slice of this wave
-            const UnitWork& w = work[u];
-            const int ent = w.id;
-            const unsigned long long mask = w.mask;
-            if (ent != -1) {
-                const int id = ent & 0x7FFFFFFF;
-                const bool fresh = ent < 0;
-                // wave = 8 x 8 columns: a square patch of the unit's xy plane projects to fewer pixel rows
-                const int x = (s & 2) * 4 + (lane >> 3), y = (s & 1) * 8 + (lane & 7);
-                const int col = x * 16 + y;
-                const int z0 = (s >> 2) * ZB;
-                float* base = d.vox + (size_t)id * (C64 ? UNIT_FLOATS_C64 : UNIT_FLOATS);
-                // colour plane c of voxel vi: float32 planes addressed from base (one address register for the
-                // whole record: a separate colour pointer costs ~34 VGPRs in this kernel), float64 through a buffer
-                // resource over the record's float64 planes
-                const __amdgpu_buffer_rsrc_t col64 = make_rsrc(base + 2 * UNIT_VOX, 3 * UNIT_VOX * 8);
-                float ts[ZB], wt[ZB];
-                CT cr[ZB], cg[ZB], cb[ZB];
-#pragma unroll
-                for (int k = 0; k < ZB; ++k) {
-                    const int vi = (z0 + k) * 256 + col;
-                    if (fresh) {
-                        ts[k] = wt[k] = 0.0f;
-                        cr[k] = cg[k] = cb[k] = (CT)0;
-                    } else {
-                        ts[k] = base[vi];
-                        wt[k] = base[UNIT_VOX + vi];
-                        if constexpr (C64) {
-                            cr[k] = ld_f64(col64, vi);
-                            cg[k] = ld_f64(col64, UNIT_VOX + vi);
-                            cb[k] = ld_f64(col64, 2 * UNIT_VOX + vi);
-                        } else {
-                            cr[k] = base[2 * UNIT_VOX + vi];
-                            cg[k] = base[3 * UNIT_VOX + vi];
-                            cb[k] = base[4 * UNIT_VOX + vi];
-                        }
-                    }
-                }
-                const float ox = (float)((double)w.kx * p.unit_len);
-                const float oy = (float)((double)w.ky * p.unit_len);
-                const float oz = (float)((double)w.kz * p.unit_len);
-                const float px = (p.half + p.vl * (float)x) + ox;
-                const float py = (p.half + p.vl * (float)y) + oy;
-                const float pz = p.half + oz;
-                const unsigned upd0 = upd;
-                if constexpr (ZB == 2) {
-                    // Frame pipeline (the fine slices serve batches with few units, whose waves cannot hide a frame's
-                    // dependent gathers behind other waves: the wave's chain of frames IS the batch's time).  Every
-                    // load of a frame is state-independent -- the projections and (depth, colour) gathers (tap), the
-                    // candidate test on d - z and the multiplier gather (stage C) -- only the update test on the scaled
-                    // distance, the clamped term and the running means (stage D) wait for it and read the voxel state.
-                    // So frame f+KT's tap and frame f+KC's stage C are issued before frame f's update,
-                    // from KT + 1 register slots (the loop is unrolled over the slots so every slot is a fixed
-                    // register set: a rotating copy would wait for the loads in flight).  The updates still run in
-                    // frame order with the same arithmetic: the bits are the unpipelined loop's.  KT = 1, KC = 0 is the
-                    // round-5 one-frame skew.
-                    constexpr int KC = KT - 1, RS = KT + 1;
-                    unsigned long long mt = mask;  // frames not yet tapped
-                    int fs[RS];                     // frame of each slot (wave-uniform), -1: past the last frame
-                    int pixv[RS][ZB];
-                    float pcz[RS][ZB], dv[RS][ZB], mv[RS][ZB], dfv[RS][ZB];
-                    uint32_t cv[RS][ZB];
-                    bool cav[RS][ZB];
-                    auto tap = [&](auto J) __attribute__((always_inline)) {
-                        constexpr int j = decltype(J)::value;
-                        if (mt) {
-                            const int f = __ffsll((long long)mt) - 1;
-                            mt &= mt - 1;
-                            fs[j] = f;
-                            frame_tap<ZB>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
-                        } else {
-                            fs[j] = -1;
-                        }
-                    };
-                    auto stage_c = [&](auto J) __attribute__((always_inline)) {
-                        constexpr int j = decltype(J)::value;
-                        if (fs[j] < 0) return;
-                        // candidates: the multiplier is >= 1, so (d - z) * m > -trunc implies d - z > -trunc -- only
-                        // these lanes gather it, from the volume's one table (stage D makes the update test itself)
-                        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            dfv[j][k] = dv[j][k] - pcz[j][k];
-                            cav[j][k] = (pixv[j][k] >= 0) & (dv[j][k] > 0.0f) & (dfv[j][k] > -p.trunc);
-                            mv[j][k] = 0.0f;
-                            if (cav[j][k])
-                                mv[j][k] = __uint_as_float(
-                                    __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, pixv[j][k] * 4, 0, 0));
-                        }
-                    };
-                    auto stage_d = [&](auto J) __attribute__((always_inline)) -> bool {
-                        constexpr int j = decltype(J)::value;
-                        if (fs[j] < 0) return false;
-                        const bool use_color = frames[fs[j]].color != nullptr;
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            const float sdf = dfv[j][k] * mv[j][k];
-                            const bool doit = cav[j][k] & (sdf > -p.trunc);
-                            const float sv = sdf * p.trunc_inv;
-                            const float tn = (sv < 1.0f) ? sv : 1.0f;
-                            const float wv = wt[k];
-                            const float w1 = wv + 1.0f;
-                            const float ta = ts[k] * wv + tn;
-                            float tsn;
-                            const double y64 = (FAST && C64) ? s_r64[(int)w1] : 0.0;
-                            if constexpr (FAST) {
-                                const float y = C64 ? (float)y64 : s_r32[(int)w1];
-                                const float q0 = ta * y;
-                                tsn = __builtin_fmaf(__builtin_fmaf(-w1, q0, ta), y, q0);
-                            } else {
-                                tsn = ta / w1;
-                            }
-                            ts[k] = doit ? tsn : ts[k];
-                            if (use_color) {
-                                const uint32_t c = cv[j][k];
-                                if constexpr (C64) {
-                                    const double wd = (double)wv, w1d = (double)w1;
-                                    const double ar = cr[k] * wd + (double)(c & 0xFFu);
-                                    const double ag = cg[k] * wd + (double)((c >> 8) & 0xFFu);
-                                    const double ab = cb[k] * wd + (double)((c >> 16) & 0xFFu);
-                                    double nr, ng, nb;
-                                    if constexpr (FAST) {
-                                        const double y = y64;
-                                        const double q0r = ar * y, q0g = ag * y, q0b = ab * y;
-                                        nr = __builtin_fma(__builtin_fma(-w1d, q0r, ar), y, q0r);
-                                        ng = __builtin_fma(__builtin_fma(-w1d, q0g, ag), y, q0g);
-                                        nb = __builtin_fma(__builtin_fma(-w1d, q0b, ab), y, q0b);
-                                    } else {
-                                        nr = ar / w1d;
-                                        ng = ag / w1d;
-                                        nb = ab / w1d;
-                                    }
-                                    cr[k] = doit ? nr : cr[k];
-                                    cg[k] = doit ? ng : cg[k];
-                                    cb[k] = doit ? nb : cb[k];
-                                } else {
-                                    const float rw = __builtin_amdgcn_rcpf(w1);
-                                    const float nr = ((float)cr[k] * wv + (float)(c & 0xFFu)) * rw;
-                                    const float ng = ((float)cg[k] * wv + (float)((c >> 8) & 0xFFu)) * rw;
-                                    const float nb = ((float)cb[k] * wv + (float)((c >> 16) & 0xFFu)) * rw;
-                                    cr[k] = doit ? nr : cr[k];
-                                    cg[k] = doit ? ng : cg[k];
-                                    cb[k] = doit ? nb : cb[k];
-                                }
-                            }
-                            wt[k] = doit ? w1 : wv;
-                            upd += doit ? 1u : 0u;
-                        }
-                        return true;
-                    };
-                    // one iteration = frame f in slot J: stage C of f + KC, the tap of f + KT (into the slot frame f - 1
-                    // left), the update of f
-                    auto iter = [&](auto J) __attribute__((always_inline)) -> bool {
-                        constexpr int j = decltype(J)::value;
-                        stage_c(std::integral_constant<int, (j + KC) % RS>{});
-                        tap(std::integral_constant<int, (j + KT) % RS>{});
-                        return stage_d(J);
-                    };
-                    // prologue: taps of the first KT frames, stage C of the first KC
-                    static_for<KT>(tap);
-                    static_for<KC>(stage_c);
-                    while (static_all<RS>(iter)) {
-                    }
-                } else {
-                    for (unsigned long long m = mask; m; m &= m - 1) {
-                        const int f = __ffsll((long long)m) - 1;
-                        const BatchFrame& fr = frames[f];
-                        const __amdgpu_buffer_rsrc_t dc_rsrc = make_rsrc(fr.dc, npx * 8);
-                        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
-                        const bool use_color = fr.color != nullptr;
-                        float pc[3];
-                        // per-frame copies of the voxel column's position: the compiler pairs the rows' products
-                        // (packed float32 math) and would otherwise keep px, py, pz duplicated in register pairs across
-                        // the whole frame loop (8 VGPRs for 3 values: the float64-colour kernel then spills)
-                        float fpx = px, fpy = py, fpz = pz;
-                        asm volatile("" : "+v"(fpx), "+v"(fpy), "+v"(fpz));
-#pragma unroll
-                        for (int r = 0; r < 3; ++r) {
-                            const float a = fr.E[r * 4 + 0] * fpx;
-                            const float b = fr.E[r * 4 + 1] * fpy;
-                            const float c = fr.E[r * 4 + 2] * fpz;
-                            pc[r] = ((a + b) + c) + fr.E[r * 4 + 3];
-                        }
-                        const float es0 = fr.es[0], es1 = fr.es[1], es2 = fr.es[2];
-                        for (int k = 0; k < z0; ++k) {  // wave-uniform: advance to this slice's first voxel
-                            pc[0] += es0;
-                            pc[1] += es1;
-                            pc[2] += es2;
-                        }
-                        // phase A: projections of the ZB voxels
-                        int pixv[ZB];
-                        float pcz[ZB];
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            const float nu = pc[0] * p.fx, nv = pc[1] * p.fy;
-                            // Certified fast projection.  Only floor(u), floor(v) and the bound tests are used, so
-                            // u = nu * rcp(z) decides them exactly unless u lies within proj_eps of an integer (the
-                            // bound tests 0.0001 and W - 0.0001 sit 1e-4 from integers); those rare waves redo the
-                            // IEEE quotients.
-                            const float rz = __builtin_amdgcn_rcpf(pc[2]);
-                            float u_f = (nu * rz + p.cx) + 0.5f;
-                            float v_f = (nv * rz + p.cy) + 0.5f;
-                            const bool sure = !(pc[2] > 0.0f) ||
-                                              ((int)(fabsf(u_f - __builtin_rintf(u_f)) > p.proj_eps) &
-                                               (int)(fabsf(v_f - __builtin_rintf(v_f)) > p.proj_eps));
-                            if (!sure) {
-                                u_f = ((nu / pc[2]) + p.cx) + 0.5f;
-                                v_f = ((nv / pc[2]) + p.cy) + 0.5f;
-                            }
-                            // non-short-circuit test keeps all ZB projections in one basic block
-                            const bool ok = (pc[2] > 0.0f) & (u_f >= 0.0001f) & (u_f < p.safe_w) & (v_f >= 0.0001f) &
-                                            (v_f < p.safe_h);
-                            pixv[k] = ok ? (int)__umul24((unsigned)(int)v_f, (unsigned)p.W) + (int)u_f : -1;
-                            pcz[k] = pc[2];
-                            pc[0] += es0;
-                            pc[1] += es1;
-                            pc[2] += es2;
-                        }
-                        // phase B: every depth gather issued before any use (buffer loads: wave-uniform resource +
-                        // 32-bit byte offset, no per-lane 64-bit address math)
-                        float dv[ZB];
-                        uint32_t cv[ZB];
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            dv[k] = 0.0f;
-                            cv[k] = 0u;
-                            if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
-                                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, pixv[k] * 8, 0, 0);
-                                dv[k] = __uint_as_float(raw.x);
-                                cv[k] = raw.y;
-                            }
-                        }
-                        // phase C: the depth test.  The ray multiplier (the volume's one table, not a per-frame copy)
-                        // is gathered only by the candidate lanes: it is >= 1 and rounding is monotone, so
-                        // (d - z) * m > -trunc implies d - z > -trunc; the test on the product is then Open3D's
-                        bool doitv[ZB];
-                        float sdfv[ZB];
-                        unsigned mv[ZB];  // the gather's byte offset, then its result in the same register (the other
-                                          // lanes keep the offset: their product is never selected)
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            sdfv[k] = dv[k] - pcz[k];
-                            doitv[k] = (pixv[k] >= 0) & (dv[k] > 0.0f) & (sdfv[k] > -p.trunc);
-                            mv[k] = (unsigned)pixv[k] * 4u;
-                            if (doitv[k]) mv[k] = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, (int)mv[k], 0, 0);
-                        }
-                        // phase D: updates in frame order (select form: identical values, no exec-mask branches)
-#pragma unroll
-                        for (int k = 0; k < ZB; ++k) {
-                            const float sdf = sdfv[k] * __uint_as_float(mv[k]);
-                            const bool doit = doitv[k] & (sdf > -p.trunc);
-                            const float sv = sdf * p.trunc_inv;
-                            const float tn = (sv < 1.0f) ? sv : 1.0f;
-                            const float wv = wt[k];
-                            const float w1 = wv + 1.0f;
-                            const float ta = ts[k] * wv + tn;
-                            float tsn;  // (tsdf * w + t) / (w + 1): the IEEE quotient, tsdf bit-exact
-                            // one table read per voxel for the tsdf and the colour quotients (round 3: +0.8 %)
-                            const double y64 = (FAST && C64) ? s_r64[(int)w1] : 0.0;
-                            if constexpr (FAST) {
-                                const float y = C64 ? (float)y64 : s_r32[(int)w1];
-                                const float q0 = ta * y;
-                                tsn = __builtin_fmaf(__builtin_fmaf(-w1, q0, ta), y, q0);
-                            } else {
-                                tsn = ta / w1;
-                            }
-                            ts[k] = doit ? tsn : ts[k];
-                            if (use_color) {
-                                if constexpr (C64) {  // Open3D: color = (color * weight + rgb) / (weight + 1.0f) in float64
-                                    {  // every lane, in select form (skipping voxels without an updating lane: slower)
-                                        const double wd = (double)wv, w1d = (double)w1;
-                                        const double ar = cr[k] * wd + (double)(cv[k] & 0xFFu);
-                                        const double ag = cg[k] * wd + (double)((cv[k] >> 8) & 0xFFu);
-                                        const double ab = cb[k] * wd + (double)((cv[k] >> 16) & 0xFFu);
-                                        double nr, ng, nb;
-                                        if constexpr (FAST) {
-                                            const double y = y64;
-                                            const double q0r = ar * y, q0g = ag * y, q0b = ab * y;
-                                            nr = __builtin_fma(__builtin_fma(-w1d, q0r, ar), y, q0r);
-                                            ng = __builtin_fma(__builtin_fma(-w1d, q0g, ag), y, q0g);
-                                            nb = __builtin_fma(__builtin_fma(-w1d, q0b, ab), y, q0b);
-                                        } else {
-                                            nr = ar / w1d;
-                                            ng = ag / w1d;
-                                            nb = ab / w1d;
-                                        }
-                                        cr[k] = doit ? nr : cr[k];
-                                        cg[k] = doit ? ng : cg[k];
-                                        cb[k] = doit ? nb : cb[k];
-                                    }
-                                } else {  // float32 state, one reciprocal for the three channels (|rel| <= 1e-4)
-                                    const float rw = __builtin_amdgcn_rcpf(w1);
-                                    const float nr = ((float)cr[k] * wv + (float)(cv[k] & 0xFFu)) * rw;
-                                    const float ng = ((float)cg[k] * wv + (float)((cv[k] >> 8) & 0xFFu)) * rw;
-                                    const float nb = ((float)cb[k] * wv + (float)((cv[k] >> 16) & 0xFFu)) * rw;
-                                    cr[k] = doit ? nr : cr[k];
-                                    cg[k] = doit ? ng : cg[k];
-                                    cb[k] = doit ? nb : cb[k];
-                                }
-                            }
-                            wt[k] = doit ? w1 : wv;
-                            upd += doit ? 1u : 0u;
-                        }
-                    }
-                }
-                // a slice none of whose voxels updated in this batch still holds its HBM values (fresh ones: zeros)
-                if (!fresh && !__any(upd != upd0)) continue;
-#pragma unroll
-                for (int k = 0; k < ZB; ++k) {
-                    const int vi = (z0 + k) * 256 + col;
-                    base[vi] = ts[k];
-                    base[UNIT_VOX + vi] = wt[k];
-                    if constexpr (C64) {
-                        st_f64(col64, vi, cr[k]);
-                        st_f64(col64, UNIT_VOX + vi, cg[k]);
-                        st_f64(col64, 2 * UNIT_VOX + vi, cb[k]);
-                    } else {
-                        base[2 * UNIT_VOX + vi] = cr[k];
-                        base[3 * UNIT_VOX + vi] = cg[k];
-                        base[4 * UNIT_VOX + vi] = cb[k];
-                    }
-                }
-            }
-        }
-    }
-    const unsigned long long tot = wave_sum((unsigned long long)upd);
-    if (lane == 0 && tot) atomicAdd(&d.stats[S_UPDATES], tot);
+    integrate_body<C64, FAST, ZB, KT, false>(frames, p, d, work, wcount, s_r32, s_r64, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The deferred integrate of a sharded volume's batch k and the touch of batch k + 1 in ONE launch (round 6): workgroups
@@ -1598,8 +1186,10 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : IN
 // GPU per batch: the double-buffered front end).  The touch writes only batch k + 1's state: its frame
 // masks / slot list / pair counter, hash inserts of its units, and the staged pixels of its samples in its own set --
 // nothing the integrate of batch k reads.  LDS: the touch's tables and the reciprocal table share one block.
+// The IEEE-division float64 integrate needs 67 VGPRs: it takes the 5-wave bound k_batch_integrate gives it (under the
+// 8-wave bound it spilled 20-32 B inside the frame loop; per launch the two measure the same).
 template <bool C64, bool FAST>
-__global__ __launch_bounds__(64 * INT_WG, INT_WAVES_PER_EU) void k_integrate_touch(
+__global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : INT_WAVES_PER_EU) void k_integrate_touch(
     const BatchFrame* __restrict__ frames, IntegrateParams p, TsdfDev d, const UnitWork* __restrict__ work,
     const int* __restrict__ wcount, int nint, const BatchFrame* __restrict__ tframes, BatchTouchParams tp, int tn) {
     union Lds {
@@ -1609,7 +1199,7 @@ __global__ __launch_bounds__(64 * INT_WG, INT_WAVES_PER_EU) void k_integrate_tou
     __shared__ Lds lds;
     const int b = (int)blockIdx.x;
     if (b < nint) {
-        integrate_body<C64, FAST, BZ, 1>(frames, p, d, work, wcount, lds.r, b, nint);
+        integrate_body<C64, FAST, BZ, 1, true>(frames, p, d, work, wcount, lds.r.r32, lds.r.r64, b, nint);
     } else {
         const int t = b - nint;
         touch_body<false, false>(tframes, tp, d, tn, lds.t, t % tp.tiles, t / tp.tiles);
@@ -1629,7 +1219,7 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : 4) void k_integra
     __shared__ Lds lds;
     const int b = (int)blockIdx.x;
     if (b < nint) {
-        integrate_body<C64, FAST, 2, 1>(frames, p, d, work, wcount, lds.r, b, nint);
+        integrate_body<C64, FAST, 2, 1, true>(frames, p, d, work, wcount, lds.r.r32, lds.r.r64, b, nint);
     } else {
         const int t = b - nint;
         touch_body<false, false>(tframes, tp, d, tn, lds.t, t % tp.tiles, t / tp.tiles);

@@ -142,6 +142,52 @@ def test_fine_slices_forced(pkg, O, gpu, synth, depth):
         L.call("otx_integrate_depth", -1)
 
 
+FORMS = {  # hook -> value; the hooks not named stay at -1
+    "coarse": {"otx_integrate_fine": 0},
+    "fine1": {"otx_integrate_fine": 1, "otx_integrate_depth": 1},
+    "fine2": {"otx_integrate_fine": 1, "otx_integrate_depth": 2},
+    "fine3": {"otx_integrate_fine": 1, "otx_integrate_depth": 3},
+    "deferred_coarse": {"otx_split_frontend": 1, "otx_defer_integrate": 1, "otx_integrate_fine": 0},
+    "deferred_fine": {"otx_split_frontend": 1, "otx_defer_integrate": 1, "otx_integrate_fine": 1},
+}
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("division", ["table", "ieee"])
+@pytest.mark.parametrize("precision", [64, 32])
+def test_every_integrate_instantiation(pkg, O, gpu, synth, precision, division, form):
+    """Every instantiation of the integrate (colour precision x division form x slice form: k_batch_integrate coarse
+    and fine at pipeline depths 1-3, k_integrate_touch and k_integrate_touch_fine) on the wide-camera wall scan.
+    table: a fresh volume, 6 frames in batches of 4 -- a deferred batch is launched once fused with the next touch and
+    once alone by the flush.  ieee: the route of test_ieee_division_kernel_after_import -- volume A integrates the
+    first 3 frames and exports, volume B imports A's units (arbitrary state: the IEEE-division kernels) and integrates
+    the other 3 in batches of 2 with the form forced; the oracle integrates all six (voxel state; B's counters are the
+    oracle's for the last three frames)."""
+    depth, color, ext = _frames(synth, WIDE, ORBIT)
+    ref = _oracle(O, synth, WIDE, ORBIT, True)
+    L = pkg._lib
+    if division == "table":
+        vol, first = _volume(pkg, True, 4, precision), 0
+    else:
+        a = _volume(pkg, True, None, precision)
+        _integrate(pkg, a, WIDE, depth[:3], color[:3], ext[:3])
+        vol, first = _volume(pkg, True, 2, precision), 3
+        vol.import_units(*a.export_units())
+        # the counters count a volume's own integrations, and both are sums over frames (voxel updates; (unit, frame)
+        # integrations): A's are the oracle's for the first 3 frames, so B's must be the six-frame oracle's less those
+        upd3, units3 = _oracle(O, synth, WIDE, ORBIT[:3], True)[4:]
+        assert tuple(a.counters()) == (upd3, units3)
+        ref = ref[:4] + (ref[4] - upd3, ref[5] - units3)
+    try:
+        for hook, value in FORMS[form].items():
+            L.call(hook, value)
+        _integrate(pkg, vol, WIDE, depth[first:], color[first:], ext[first:])
+        assert _compare(vol, ref, True) > 100
+    finally:
+        for hook in ("otx_integrate_fine", "otx_integrate_depth", "otx_split_frontend", "otx_defer_integrate"):
+            L.call(hook, -1)
+
+
 def test_reciprocal_table_bound(pkg, O, gpu, synth):
     """9 frames from one pose in batches of 4 (4, 4, 1): voxels seen every time reach weight 9, the last entry the last
     batch's table holds (frames since reset + the batch's).  Then a reset and 3 more frames (the bound starts again
