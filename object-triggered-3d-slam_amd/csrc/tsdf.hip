@@ -807,10 +807,15 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
         pc[r] = ((a + b) + c) + fr.E[r * 4 + 3];
     }
     const float es0 = fr.es[0], es1 = fr.es[1], es2 = fr.es[2];
-    for (int k = 0; k < z0; ++k) {  // wave-uniform: advance to this slice's first voxel
-        pc[0] += es0;
-        pc[1] += es1;
-        pc[2] += es2;
+    // wave-uniform: advance to this slice's first voxel by the same sequence of adds, ZB to a trip (z0 is a multiple
+    // of ZB): one taken branch per ZB steps instead of one per step
+    for (int k = 0; k < z0; k += ZB) {
+#pragma unroll
+        for (int j = 0; j < ZB; ++j) {
+            pc[0] += es0;
+            pc[1] += es1;
+            pc[2] += es2;
+        }
     }
     // phase A: projections of the ZB voxels
 #pragma unroll
@@ -850,30 +855,27 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
     }
 }
 
-// Phase C of one frame, state-independent too: the candidate test on df = d - z.  The ray multiplier (the volume's one
-// table, not a per-frame copy) is gathered only by the candidate lanes: it is >= 1 and rounding is monotone, so
-// (d - z) * m > -trunc implies d - z > -trunc; the update's test on the product is then Open3D's.  mv: the gathered
-// multiplier's float bits on the candidate lanes.  On the other lanes it is not a multiplier -- SHARE (the coarse loop):
-// the gather's byte offset, offset and result in one register, which the 64-VGPR float64-colour kernel needs; !SHARE
-// (the fine pipeline's slots, 3-4 % faster per launch so): zero -- so df * mv may be anything there, NaN included;
-// cand is false on those lanes and voxel_update only selects.  Use mv or the product outside a select on cand nowhere.
-template <int ZB, bool SHARE>
-__device__ __forceinline__ void frame_candidates(const IntegrateParams& p, int npx, const int (&pixv)[ZB],
-                                                 const float (&pcz)[ZB], const float (&dv)[ZB], bool (&cand)[ZB],
-                                                 float (&df)[ZB], unsigned (&mv)[ZB]) {
-    const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
-#pragma unroll
-    for (int k = 0; k < ZB; ++k) {
-        df[k] = dv[k] - pcz[k];
-        cand[k] = (pixv[k] >= 0) & (dv[k] > 0.0f) & (df[k] > -p.trunc);
-        if constexpr (SHARE) {
-            mv[k] = (unsigned)pixv[k] * 4u;
-            if (cand[k]) mv[k] = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, (int)mv[k], 0, 0);
-        } else {
-            mv[k] = 0u;
-            if (cand[k]) mv[k] = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, pixv[k] * 4, 0, 0);
-        }
-    }
+// Phase C of one frame, state-independent too, in two pieces per voxel.  The test: the candidate lanes on df = d - z.
+// The ray multiplier m is >= 1 and rounding is monotone, so (d - z) * m > -trunc implies d - z > -trunc: cand is a
+// superset of the updating lanes and needs no m; the update's test on the product is then Open3D's.  A frame none of
+// whose lanes is a candidate for any of the wave's voxels ends there for a coarse wave (integrate_frames): cand false
+// already meant "select the old value" on every lane, so nothing after the test can change a voxel, the update count
+// or the write-back decision.
+__device__ __forceinline__ bool voxel_candidate(const IntegrateParams& p, int pix, float pcz, float dv, float& df) {
+    df = dv - pcz;
+    return (pix >= 0) & (dv > 0.0f) & (df > -p.trunc);
+}
+// The multiplier gather (the volume's one table, not a per-frame copy), by the candidate lanes only: the gathered
+// multiplier's float bits on the candidate lanes.  On the other lanes the result is not a multiplier -- SHARE (the
+// coarse loop): the gather's byte offset, offset and result in one register, which the 64-VGPR float64-colour kernel
+// needs; !SHARE (the fine pipeline's slots, 3-4 % faster per launch so): zero -- so df * mv may be anything there, NaN
+// included; cand is false on those lanes and voxel_update only selects.  Use mv or the product outside a select on
+// cand nowhere.
+template <bool SHARE>
+__device__ __forceinline__ unsigned voxel_multiplier(const __amdgpu_buffer_rsrc_t& mult_rsrc, int pix, bool cand) {
+    unsigned mv = SHARE ? (unsigned)pix * 4u : 0u;
+    if (cand) mv = __builtin_amdgcn_raw_buffer_load_b32(mult_rsrc, SHARE ? (int)mv : pix * 4, 0, 0);
+    return mv;
 }
 
 // Phase D for one voxel and one frame: the update of a candidate lane whose scaled distance sdf = (d - z) * m passes
@@ -961,7 +963,16 @@ __device__ __forceinline__ void integrate_frames(const BatchFrame* __restrict__ 
         bool cand[ZB];
         unsigned mv[ZB];
         frame_tap<ZB>(fr, p, npx, fpx, fpy, fpz, z0, pixv, pcz, dv, cv);
-        frame_candidates<ZB, true>(p, npx, pixv, pcz, dv, cand, df, mv);
+        bool some = false;
+#pragma unroll
+        for (int k = 0; k < ZB; ++k) some |= cand[k] = voxel_candidate(p, pixv[k], pcz[k], dv[k], df[k]);
+        // an idle wave-frame (no candidate lane: the surface is elsewhere in this frame, or its depth is missing) leaves
+        // before the multiplier gathers, the reciprocal reads and the updates -- the loop's one new uniform branch, a
+        // scalar compare of the lane mask
+        if (__builtin_amdgcn_ballot_w64(some) == 0ull) continue;
+        const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
+#pragma unroll
+        for (int k = 0; k < ZB; ++k) mv[k] = voxel_multiplier<true>(mult_rsrc, pixv[k], cand[k]);
         // updates in frame order
 #pragma unroll
         for (int k = 0; k < ZB; ++k)
@@ -1031,8 +1042,8 @@ __device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ fr
         // Frame pipeline (the fine slices serve batches with few units, whose waves cannot hide a frame's dependent
         // gathers behind other waves: the wave's chain of frames IS the batch's time).  Every load of a frame is
         // state-independent -- the projections and (depth, colour) gathers (frame_tap), the candidate test and the
-        // multiplier gather (frame_candidates) -- only the update (voxel_update) waits for it and reads the voxel
-        // state.  So frame f+KT's tap and frame f+KC's candidate stage are issued before frame f's update, from
+        // multiplier gather (voxel_candidate, voxel_multiplier) -- only the update (voxel_update) waits for it and reads
+        // the voxel state.  So frame f+KT's tap and frame f+KC's candidate stage are issued before frame f's update, from
         // KT + 1 register slots (the loop is unrolled over the slots so every slot is a fixed register set: a
         // rotating copy would wait for the loads in flight).  The updates still run in frame order with the same
         // arithmetic: the bits are the unpipelined loop's.  KT = 1, KC = 0 is the round-5 one-frame skew.
@@ -1060,7 +1071,12 @@ __device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ fr
         auto stage_c = [&](auto J) __attribute__((always_inline)) {
             constexpr int j = decltype(J)::value;
             if (fs[j] < 0) return;
-            frame_candidates<ZB, false>(p, npx, pixv[j], pcz[j], dv[j], cand[j], df[j], mv[j]);
+            const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
+#pragma unroll
+            for (int k = 0; k < ZB; ++k) {  // test and gather voxel by voxel: no frame is left early here
+                cand[j][k] = voxel_candidate(p, pixv[j][k], pcz[j][k], dv[j][k], df[j][k]);
+                mv[j][k] = voxel_multiplier<false>(mult_rsrc, pixv[j][k], cand[j][k]);
+            }
         };
         auto stage_d = [&](auto J) __attribute__((always_inline)) -> bool {
             constexpr int j = decltype(J)::value;
@@ -1090,9 +1106,15 @@ __device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ fr
     upd += iu;
     // a slice none of whose voxels updated in this batch still holds its HBM values (fresh ones: zeros)
     if (!fresh && !__any(iu != 0u)) return;
+    // the write-back's column from a second copy of the thread index, so that no voxel index lives through the frame
+    // loop (with the idle-frame branch in it the fused float64 kernel spilled one)
+    unsigned tidw = threadIdx.x;
+    asm volatile("" : "+v"(tidw));
+    const int lanew = tidw & 63;
+    const int colw = ((s & 2) * 4 + (lanew >> 3)) * 16 + (s & 1) * 8 + (lanew & 7);
 #pragma unroll
     for (int k = 0; k < ZB; ++k) {
-        const int vi = (z0 + k) * 256 + col;
+        const int vi = (z0 + k) * 256 + colw;
         base[vi] = ts[k];
         base[UNIT_VOX + vi] = wt[k];
         if constexpr (C64) {
