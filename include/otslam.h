@@ -111,6 +111,35 @@ ot_status ot_gather_rows3(const double* in, const int64_t* idx, int64_t m, doubl
 ot_status ot_compute_point_cloud_distance(const double* src, int64_t n, const double* tgt, int64_t m,
                                           double* out, void* stream);
 
+/* geometry.PointCloud.transform(T) — eval_cone.py:96.  T_host: row-major 4x4 on the host.  Per point (Eigen's
+ * column-order product, no contraction): x' = ((T00 x + T01 y) + T02 z) + T03 (rows 1..3 alike), then xyz' / w'.
+ * normals (nullable, with out_normals) are multiplied by the upper 3x3 block and not renormalised.  out may alias
+ * the input. */
+ot_status ot_transform_points(const double* xyz, const double* normals, int64_t n, const double T_host[16],
+                              double* out_xyz, double* out_normals, void* stream);
+
+/* pipelines.registration.evaluate_registration(source, target, max_correspondence_distance, T) (DESIGN.md §4,
+ * "registration"): pcd = T source; per pcd point the nearest target point by exact float64 squared distance
+ * ((dx dx + dy dy) + dz dz; equidistant targets: the lowest index), a correspondence iff d2 < r r (strict);
+ * fitness = k / n, inlier_rmse = sqrt(sum d2 / k), both 0 when k = 0.  corr (device int32 [n][2], nullable) receives
+ * the k (source index, target index) pairs in ascending source index.  Empty source or target, or
+ * max_corr_dist <= 0: zeros, no pairs. */
+ot_status ot_evaluate_registration(const double* src, int64_t n, const double* tgt, int64_t m, double max_corr_dist,
+                                   const double T_host[16], double* fitness_host, double* rmse_host, int32_t* corr,
+                                   int64_t* n_corr_host, void* stream);
+
+/* pipelines.registration.registration_icp(source, target, max_correspondence_distance, init,
+ * TransformationEstimationPointToPoint(), ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration))
+ * — eval_cone.py:89-97.  Each iteration fits the rigid update of the current correspondences (Eigen::umeyama without
+ * scaling), moves the kept cloud by it, re-evaluates, and stops once fitness and inlier_rmse both change by less than
+ * their thresholds; the whole loop runs on the device.  Outputs as ot_evaluate_registration for the last evaluation,
+ * T_out_host = the accumulated transformation (row-major), iterations_host = fits performed.  Empty source or
+ * target: zeros, no pairs, T = init.  max_corr_dist <= 0 fails with "Invalid max_correspondence_distance." */
+ot_status ot_registration_icp(const double* src, int64_t n, const double* tgt, int64_t m, double max_corr_dist,
+                              const double init_host[16], double relative_fitness, double relative_rmse,
+                              int32_t max_iteration, double T_out_host[16], double* fitness_host, double* rmse_host,
+                              int32_t* corr, int64_t* n_corr_host, int32_t* iterations_host, void* stream);
+
 /* The configs[2] filter chain for a batch of frames, device-resident end to end (not an Open3D API: the batch form
  * of the per-frame calls below, results bit-identical to them).  Per frame f of a run:
  *   create_from_color_and_depth(depth_scale, depth_trunc) -> PointCloud.create_from_rgbd_image(intrinsic,

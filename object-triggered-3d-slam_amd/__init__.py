@@ -8,7 +8,9 @@ switches with one line:
 
     o3d.camera.PinholeCameraIntrinsic, o3d.io.read_image / read_point_cloud / write_point_cloud / ...,
     o3d.geometry.{Image, RGBDImage, PointCloud, TriangleMesh}, o3d.utility.Vector3dVector,
-    o3d.pipelines.integration.{ScalableTSDFVolume, TSDFVolumeColorType}, o3d.visualization.draw_geometries (headless)
+    o3d.pipelines.integration.{ScalableTSDFVolume, TSDFVolumeColorType},
+    o3d.pipelines.registration.{registration_icp, evaluate_registration, ICPConvergenceCriteria,
+    TransformationEstimationPointToPoint}, o3d.visualization.draw_geometries (headless)
 
 Every compute call goes through the C ABI in include/otslam.h (libotslam_hip.so, HIP kernels for gfx950).
 """

@@ -41,6 +41,7 @@ _d = C.c_double
 _i32 = C.c_int32
 _i64 = C.c_int64
 _pi64 = C.POINTER(C.c_int64)
+_pd = C.POINTER(C.c_double)
 _pint = C.POINTER(ot_intrinsics)
 
 # name -> argtypes (restype is int32 status unless listed in _RESTYPES)
@@ -55,6 +56,10 @@ SIGNATURES = {
     "ot_remove_statistical_outlier": [_p, _i64, _i32, _d, _p, _p, _pi64, _p],
     "ot_remove_radius_outlier": [_p, _i64, _i32, _d, _p, _pi64, _p],
     "ot_compute_point_cloud_distance": [_p, _i64, _p, _i64, _p, _p],
+    "ot_transform_points": [_p, _p, _i64, _p, _p, _p, _p],
+    "ot_evaluate_registration": [_p, _i64, _p, _i64, _d, _p, _pd, _pd, _p, _pi64, _p],
+    "ot_registration_icp": [_p, _i64, _p, _i64, _d, _p, _d, _d, _i32, _p, _pd, _pd, _p, _pi64, C.POINTER(C.c_int32),
+                            _p],
     "ot_filter_min_z": [_p, _p, _i64, _d, _p, _p, _pi64, _p],
     "ot_gather_rows3": [_p, _p, _i64, _p, _p],
     "ot_tsdf_create": [_d, _d, _i32, _i32, _i32, _i64, C.POINTER(_p)],
@@ -154,6 +159,7 @@ TEST_SIGNATURES = {
     "otx_sort_pairs_u64_u32": [_p, _p, _p, _p, _i64, _i32, _p],
     "otx_sort_segments_u32_u32": [_p, _p, _p, _p, _p, _i32, _i32, _p],
     "otx_alloc_count": [],
+    "otx_registration_last_d2": [_p, _i64, _p],
 }
 
 

@@ -54,6 +54,71 @@ struct GridBuild {
     int64_t ncells = 0;
 };
 
+// ---- device lookups (shared by outlier.hip and icp.hip) ----------------------------------------------------------
+__device__ inline int cell_coord(double v, double origin, double h) { return (int)floor((v - origin) / h); }
+
+__device__ inline bool cell_valid(const GridDev& g, int x, int y, int z) {
+    return x >= 0 && x < g.dim[0] && y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2];
+}
+__device__ inline unsigned long long cell_key(const GridDev& g, int f, int x, int y, int z) {
+    return ((unsigned long long)f << g.sf) | ((unsigned long long)x << g.sx) | ((unsigned long long)y << g.sy) |
+           (unsigned long long)z;
+}
+
+__device__ inline int2 grid_probe(const GridDev& g, unsigned long long key, unsigned slot) {
+    for (int probe = 0; probe <= g.hash_mask; ++probe) {
+        const unsigned long long k = g.hkeys[slot];
+        if (k == key) return g.hval[slot];
+        if (k == KEY_EMPTY) return make_int2(0, 0);
+        slot = (slot + 1) & (unsigned)g.hash_mask;
+    }
+    return make_int2(0, 0);
+}
+
+// the occupied cells of column (f, x, y): {first cell, count}
+__device__ inline int2 grid_column(const GridDev& g, int f, int x, int y) {
+    if (x < 0 || x >= g.dim[0] || y < 0 || y >= g.dim[1]) return make_int2(0, 0);
+    const unsigned long long key = cell_key(g, f, x, y, 0) >> g.sy;
+    return grid_probe(g, key, (unsigned)mix64(key) & (unsigned)g.hash_mask);
+}
+
+// points of the column's cells with zlo <= z <= zhi: one contiguous range of the sorted order (or empty)
+__device__ inline int2 column_range(const GridDev& g, int2 col, int zlo, int zhi) {
+    int b = 0, e = 0;
+    bool any = false;
+    int i0 = 0;
+    if (col.y > 8) {  // tall column (a wall seen edge-on): bisect for the first cell with z >= zlo
+        int lo = -1, hi = col.y;  // cz[lo] < zlo <= cz[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (g.cz[col.x + mid] < zlo) lo = mid;
+            else hi = mid;
+        }
+        i0 = hi;
+    }
+    for (int i = i0; i < col.y; ++i) {
+        const int z = g.cz[col.x + i];
+        if (z > zhi) break;
+        if (z >= zlo) {
+            const int2 r = g.crange[col.x + i];
+            if (!any) b = r.x;
+            e = r.y;
+            any = true;
+        }
+    }
+    return any ? make_int2(b, e) : make_int2(0, 0);
+}
+
+__device__ inline int2 grid_find(const GridDev& g, int f, int x, int y, int z) {
+    return column_range(g, grid_column(g, f, x, y), z, z);
+}
+
+
+__device__ inline double d2_l2(const double* q, const double* p) {
+    const double d0 = q[0] - p[0], d1 = q[1] - p[1], d2 = q[2] - p[2];
+    return ((d0 * d0) + d1 * d1) + d2 * d2;
+}
+
 // Build the grid of n points (xyz device [n][3]) grouped in nframes frames.  d_foff / d_origin: device arrays
 // ([F+1] ints, [F][3] doubles) that must outlive the grid; dims: cells per axis covering every frame; nbr: the
 // GRID_* structures to precompute; h_foff (optional host copy of the frame offsets, <= 64 frames): the cell sort
@@ -82,6 +147,19 @@ ot_status sor_frames(const GridBuild& gb, int64_t n, const int* h_foff, int nb_n
 // host frame offsets) to stats[f] = {mean, std, valid, threshold}.  Scratch slot `slot`.  Synchronises once.
 ot_status sor_stats_frames(const double* avg, const int* d_foff, const int* h_foff, int F, double std_ratio,
                            double* stats, hipStream_t stream, int slot);
+
+// per-axis bounds of a device cloud on the host (scratch slots 11, 19).  Synchronises.
+ot_status bounds_host(const double* xyz, int64_t n, hipStream_t stream, double mn[3], double mx[3]);
+
+// one frame: origin = the cloud's minimum corner, cells per axis from the extent (scratch slots 20, 22 .. 24)
+ot_status single_frame_grid(const double* xyz, int64_t n, double h, const double mn[3], const double mx[3], int nbr,
+                            hipStream_t stream, GridBuild& gb);
+
+// The grid a cross-cloud nearest-neighbour search runs over (ComputePointCloudDistance, registration): the target's
+// bounds and cells sized for ~4 target points per occupied cell of a surface-like cloud, refined once from the
+// measured occupancy.  The grid only changes speed, never a result.  Scratch slots as above.  Synchronises.
+ot_status nn_target_grid(const double* tgt, int64_t m, int nbr, hipStream_t stream, double mn[3], double mx[3],
+                         GridBuild& gb);
 
 // keep predicate of frame f's points: avg > 0 && avg < stats[f].threshold
 struct SorKeep {

@@ -27,64 +27,6 @@
 
 namespace ot {
 
-__device__ inline int cell_coord(double v, double origin, double h) { return (int)floor((v - origin) / h); }
-
-__device__ inline bool cell_valid(const GridDev& g, int x, int y, int z) {
-    return x >= 0 && x < g.dim[0] && y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2];
-}
-__device__ inline unsigned long long cell_key(const GridDev& g, int f, int x, int y, int z) {
-    return ((unsigned long long)f << g.sf) | ((unsigned long long)x << g.sx) | ((unsigned long long)y << g.sy) |
-           (unsigned long long)z;
-}
-
-__device__ inline int2 grid_probe(const GridDev& g, unsigned long long key, unsigned slot) {
-    for (int probe = 0; probe <= g.hash_mask; ++probe) {
-        const unsigned long long k = g.hkeys[slot];
-        if (k == key) return g.hval[slot];
-        if (k == KEY_EMPTY) return make_int2(0, 0);
-        slot = (slot + 1) & (unsigned)g.hash_mask;
-    }
-    return make_int2(0, 0);
-}
-
-// the occupied cells of column (f, x, y): {first cell, count}
-__device__ inline int2 grid_column(const GridDev& g, int f, int x, int y) {
-    if (x < 0 || x >= g.dim[0] || y < 0 || y >= g.dim[1]) return make_int2(0, 0);
-    const unsigned long long key = cell_key(g, f, x, y, 0) >> g.sy;
-    return grid_probe(g, key, (unsigned)mix64(key) & (unsigned)g.hash_mask);
-}
-
-// points of the column's cells with zlo <= z <= zhi: one contiguous range of the sorted order (or empty)
-__device__ inline int2 column_range(const GridDev& g, int2 col, int zlo, int zhi) {
-    int b = 0, e = 0;
-    bool any = false;
-    int i0 = 0;
-    if (col.y > 8) {  // tall column (a wall seen edge-on): bisect for the first cell with z >= zlo
-        int lo = -1, hi = col.y;  // cz[lo] < zlo <= cz[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (g.cz[col.x + mid] < zlo) lo = mid;
-            else hi = mid;
-        }
-        i0 = hi;
-    }
-    for (int i = i0; i < col.y; ++i) {
-        const int z = g.cz[col.x + i];
-        if (z > zhi) break;
-        if (z >= zlo) {
-            const int2 r = g.crange[col.x + i];
-            if (!any) b = r.x;
-            e = r.y;
-            any = true;
-        }
-    }
-    return any ? make_int2(b, e) : make_int2(0, 0);
-}
-
-__device__ inline int2 grid_find(const GridDev& g, int f, int x, int y, int z) {
-    return column_range(g, grid_column(g, f, x, y), z, z);
-}
-
 // the cell the grid assigned to sorted point j (its key): SOR measures every guard from this cell's faces, so a
 // point the rounding of its coordinates puts a hair outside its cell still gets correct (conservative) bounds
 __device__ inline void query_cell(const GridDev& g, int64_t j, int& cx, int& cy, int& cz) {
@@ -194,11 +136,6 @@ __global__ __launch_bounds__(256) void k_gather_sorted(const double* __restrict_
     if (t >= n * 3) return;
     const int64_t j = t / 3, a = t % 3;
     sxyz[t] = xyz[(int64_t)sidx[j] * 3 + a];
-}
-
-__device__ inline double d2_l2(const double* q, const double* p) {
-    const double d0 = q[0] - p[0], d1 = q[1] - p[1], d2 = q[2] - p[2];
-    return ((d0 * d0) + d1 * d1) + d2 * d2;
 }
 
 // ------------------------------------------------------------------------------------------------ ROR
@@ -1080,7 +1017,7 @@ ot_status sor_stats_frames(const double* avg, const int* d_foff, const int* h_fo
 
 using namespace ot;
 
-static ot_status bounds_host(const double* xyz, int64_t n, hipStream_t stream, double mn[3], double mx[3]) {
+ot_status ot::bounds_host(const double* xyz, int64_t n, hipStream_t stream, double mn[3], double mx[3]) {
     Bounds* b = (Bounds*)scratch(sizeof(Bounds) + 64, 11);
     if (!b) return fail(OT_ERR_HIP, "scratch allocation failed");
     unsigned long long* part = (unsigned long long*)scratch(sizeof(unsigned long long) * BOUNDS_BLOCKS * 6, 19);
@@ -1099,7 +1036,7 @@ static ot_status bounds_host(const double* xyz, int64_t n, hipStream_t stream, d
 
 // one frame: origin = the cloud's minimum corner, cells per axis from the extent.  frame_dev receives the device
 // origin [3] and offsets {0, n} (scratch slot 20).
-static ot_status single_frame_grid(const double* xyz, int64_t n, double h, const double mn[3], const double mx[3],
+ot_status ot::single_frame_grid(const double* xyz, int64_t n, double h, const double mn[3], const double mx[3],
                                    int nbr, hipStream_t stream, GridBuild& gb) {
     int dims[3];
     for (int a = 0; a < 3; ++a) {
@@ -1115,6 +1052,28 @@ static ot_status single_frame_grid(const double* xyz, int64_t n, double h, const
     OT_HIP_TRY(hipMemcpyAsync(fr + 32, off, sizeof(off), hipMemcpyHostToDevice, stream));
     // build_grid_frames synchronises the stream before returning, so org / off outlive their copies
     return build_grid_frames(xyz, n, 1, (const int*)(fr + 32), (const double*)fr, h, dims, nbr, stream, gb, 22);
+}
+
+ot_status ot::nn_target_grid(const double* tgt, int64_t m, int nbr, hipStream_t stream, double mn[3], double mx[3],
+                             GridBuild& gb) {
+    ot_status st = bounds_host(tgt, m, stream, mn, mx);
+    if (st != OT_OK) return st;
+    // ~4 target points per occupied cell of a surface-like cloud (the grid only changes speed)
+    double ext[3];
+    for (int a = 0; a < 3; ++a) ext[a] = std::max(mx[a] - mn[a], 1e-9);
+    std::sort(ext, ext + 3);
+    const double target = 4.0;
+    const double hmin = ext[2] / 5.0e5;
+    double h = std::max(std::sqrt(0.5 * ext[2] * ext[1] * target / (double)m), hmin);
+    st = single_frame_grid(tgt, m, h, mn, mx, nbr, stream, gb);
+    if (st != OT_OK) return st;
+    const double occ = (double)m / (double)std::max<int64_t>(gb.ncells, 1);
+    if (occ > 2.5 * target || occ < 0.4 * target) {
+        h = std::max(h * std::sqrt(target / occ), hmin);
+        st = single_frame_grid(tgt, m, h, mn, mx, nbr, stream, gb);
+        if (st != OT_OK) return st;
+    }
+    return OT_OK;
 }
 
 extern "C" {
@@ -1210,24 +1169,9 @@ ot_status ot_compute_point_cloud_distance(const double* src, int64_t n, const do
         return OT_OK;
     }
     double mn[3], mx[3];
-    ot_status st = bounds_host(tgt, m, stream, mn, mx);
-    if (st != OT_OK) return st;
-    // ~4 target points per occupied cell of a surface-like cloud (the grid only changes speed)
-    double ext[3];
-    for (int a = 0; a < 3; ++a) ext[a] = std::max(mx[a] - mn[a], 1e-9);
-    std::sort(ext, ext + 3);
-    const double target = 4.0;
-    const double hmin = ext[2] / 5.0e5;
-    double h = std::max(std::sqrt(0.5 * ext[2] * ext[1] * target / (double)m), hmin);
     GridBuild gb;
-    st = single_frame_grid(tgt, m, h, mn, mx, GRID_NBR3, stream, gb);
+    ot_status st = nn_target_grid(tgt, m, GRID_NBR3, stream, mn, mx, gb);
     if (st != OT_OK) return st;
-    const double occ = (double)m / (double)std::max<int64_t>(gb.ncells, 1);
-    if (occ > 2.5 * target || occ < 0.4 * target) {
-        h = std::max(h * std::sqrt(target / occ), hmin);
-        st = single_frame_grid(tgt, m, h, mn, mx, GRID_NBR3, stream, gb);
-        if (st != OT_OK) return st;
-    }
     hipLaunchKernelGGL(k_nn_dist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, gb.g, src, n, m, mn[0],
                        mn[1], mn[2], mx[0], mx[1], mx[2], out);
     OT_LAUNCH_CHECK();

@@ -276,6 +276,78 @@ class PointCloud:
     def get_max_bound(self):
         return self._xyz.host().max(axis=0) if self.has_points() else np.zeros(3)
 
+    def get_center(self):
+        """Geometry3D::GetCenter: the mean of the points (zeros for an empty cloud); taken on the device copy when
+        that is the current one."""
+        if not self.has_points():
+            return np.zeros(3)
+        a = self._xyz
+        if a._d is not None and not a._viewed:
+            a._join()
+            return D.to_host(a._d.mean(dim=0))
+        return a.host().mean(axis=0)
+
+    def transform(self, transformation):
+        """PointCloud::Transform (eval_cone.py:96) — ot_transform_points: per point Eigen's column-order 4x4 product
+        and the division by w'; normals take the upper 3x3 block and are not renormalised.  Returns self."""
+        T = np.ascontiguousarray(np.asarray(transformation, dtype=np.float64))
+        if T.shape != (4, 4):
+            raise RuntimeError(f"[Transform] expected a 4x4 matrix, got {T.shape}")
+        n = len(self._xyz)
+        if n == 0:
+            return self
+        xyz = self._xyz.dev()
+        nrm = self._nrm.dev() if self.has_normals() else None
+        oxyz = D.empty((n, 3), "float64")
+        onrm = D.empty((n, 3), "float64") if nrm is not None else None
+        L.call("ot_transform_points", D.ptr(xyz), D.ptr(nrm), n, T.ctypes.data_as(C.c_void_p), D.ptr(oxyz),
+               D.ptr(onrm), D.stream_ptr())
+        self._xyz = _Arr(dev=oxyz)
+        if onrm is not None:
+            self._nrm = _Arr(dev=onrm)
+        return self
+
+    def rotate(self, R, center=None):
+        """Geometry3D::Rotate (eval_cone.py:85): p = R (p - center) + center, run as the rigid transform
+        [R | center - R center] through ot_transform_points (center = (0, 0, 0), the reference's call, is exactly
+        R p); normals are rotated.  center defaults to get_center().  Returns self."""
+        R = np.asarray(R, dtype=np.float64)
+        if R.shape != (3, 3):
+            raise RuntimeError(f"[Rotate] expected a 3x3 matrix, got {R.shape}")
+        c = self.get_center() if center is None else np.asarray(center, dtype=np.float64).reshape(3)
+        T = np.eye(4)
+        T[:3, :3] = R
+        for i in range(3):
+            T[i, 3] = c[i] - ((R[i, 0] * c[0] + R[i, 1] * c[1]) + R[i, 2] * c[2])
+        return self.transform(T)
+
+    def translate(self, translation, relative=True):
+        """Geometry3D::Translate (eval_cone.py:86): p + t, or p + (t - get_center()) with relative=False; one
+        elementwise float64 add on the device copy.  Returns self."""
+        t = np.asarray(translation, dtype=np.float64).reshape(3)
+        if not relative:
+            t = t - self.get_center()
+        if len(self._xyz) == 0:
+            return self
+        xyz = self._xyz.dev()
+        self._xyz = _Arr(dev=xyz + D.to_device(t))
+        return self
+
+    def __copy__(self):
+        return self.__deepcopy__({})
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy(pcd) (eval_cone.py:84): an independent cloud."""
+        out = PointCloud()
+        cp = lambda a: a.copy() if a is not None else None
+        out._xyz, out._rgb, out._nrm = cp(self._xyz), cp(self._rgb), cp(self._nrm)
+        memo[id(self)] = out
+        return out
+
+    @staticmethod
+    def get_rotation_matrix_from_xyz(rotation):
+        return get_rotation_matrix_from_xyz(rotation)
+
     def paint_uniform_color(self, color):
         """PointCloud::PaintUniformColor (hybrid_map.py:59,88)."""
         c = np.clip(np.asarray(color, dtype=np.float64).reshape(1, 3), 0.0, 1.0)
@@ -433,6 +505,17 @@ class PointCloud:
         out._xyz = _Arr(dev=oxyz[:k.value])
         out._rgb = _Arr(dev=orgb[:k.value]) if orgb is not None else None
         return out
+
+
+def get_rotation_matrix_from_xyz(rotation):
+    """open3d.geometry.get_rotation_matrix_from_xyz (eval_cone.py:83): Rx(a) Ry(b) Rz(c) for rotation = (a, b, c)
+    in radians (Eigen's AngleAxis products)."""
+    a, b, c = (float(v) for v in np.asarray(rotation, dtype=np.float64).reshape(3))
+    ca, sa, cb, sb, cc, sc = np.cos(a), np.sin(a), np.cos(b), np.sin(b), np.cos(c), np.sin(c)
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, ca, -sa], [0.0, sa, ca]])
+    ry = np.array([[cb, 0.0, sb], [0.0, 1.0, 0.0], [-sb, 0.0, cb]])
+    rz = np.array([[cc, -sc, 0.0], [sc, cc, 0.0], [0.0, 0.0, 1.0]])
+    return rx @ ry @ rz
 
 
 def _cat_host(a, b):

@@ -1,2 +1,3 @@
-"""open3d.pipelines counterpart (integration only — the reference uses nothing else from pipelines)."""
-from . import integration  # noqa: F401
+"""open3d.pipelines counterpart: integration (the reconstruction scripts) and registration (the evaluation
+scripts' ICP alignment)."""
+from . import integration, registration  # noqa: F401
