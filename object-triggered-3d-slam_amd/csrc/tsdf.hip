@@ -775,9 +775,11 @@ __device__ __forceinline__ bool static_all(F& f) {
 
 // Occupancy: the integrate lives on it: 64 VGPRs, 8 waves per SIMD for both colour precisions with
 // quarter-unit workgroups (float64 colour at 5 / 6 / 8 waves: 0.426 / 0.428 / 0.414 ms per 32-frame launch; the IEEE-
-// division float64 kernel needs more registers and runs at 5).  Measured and settled: lanes whose voxel
-// projects outside the image issue no depth gather (0.415-0.421 -> 0.409-0.412 ms); slices with no update in the
-// batch are not written back (-1.5 %).
+// division float64 kernel needs more registers and runs at 5).  Measured and settled: slices with no
+// update in the batch are not written back (-1.5 %).  The (depth, colour) gathers: in the coarse loop every lane loads,
+// a voxel outside the image from past the end of the frame (frame_tap<.., true>: -1.4 % of the headline step against the
+// exec-masked gathers, which round 1 had measured 1.5 % better on the kernel of its time); in the fine pipeline the
+// lanes outside the image issue no gather, as before.
 constexpr int INT_WAVES_PER_EU = 8;
 // Reciprocal table: y[n] = RN(1/n) for n in [1, RCP_N].  For b = w + 1 an integer in that range, q0 = RN(a*y),
 // r = fma(-b, q0, a) (exact), q = RN(q0 + r*y) is RN(a/b) -- Markstein's theorem (y correctly rounded, q0 within one
@@ -793,11 +795,29 @@ constexpr int RCP_N = 2048;  // 16 KiB (float64) / 8 KiB (float32) of LDS per wo
 // Phases A and B of one frame for a lane's ZB voxels at column position (px, py, pz), slice start z0: the certified
 // projections and the (depth, colour) gathers.  No voxel state is read, so the fine slices' frame pipeline issues them
 // ahead of earlier frames' updates (integrate_item).
-template <int ZB>
+// LINE: the coarse loop's straight-line form -- the unsure lanes' exact quotients out of line behind
+// one wave-uniform branch, a certified lane's image bounds from its integer pixel, and a gather by every lane, the
+// voxels outside the image from past the end of the frame.  !LINE: the fine pipeline's form -- the exact quotients and
+// the gathers in exec-masked regions, -1 for a voxel outside the image.
+//
+// A pixel index no frame has (check_frame: W * H < PIX_NONE): as an unsigned byte offset it is 2^31 into the 8-B
+// records, past the end of the frame without 32-bit wrap-around (offset + access size stays below 2^32, where -1 * 8 + 8
+// would wrap to 0), so the descriptor's range check answers 0 (make_rsrc).
+constexpr unsigned PIX_NONE = 1u << 28;
+
+// floor(x) as an integer, saturating, NaN -> 0: one instruction for any x (a C++ conversion is undefined out of range)
+__device__ __forceinline__ int floor_to_int(float x) {
+    int i;
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(i) : "v"(x));
+    return i;
+}
+
+template <int ZB, bool LINE>
 __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateParams& p, int npx, float px, float py,
                                           float pz, int z0, int (&pixv)[ZB], float (&pcz)[ZB], float (&dv)[ZB],
                                           uint32_t (&cv)[ZB]) {
     const __amdgpu_buffer_rsrc_t dc_rsrc = make_rsrc(fr.dc, npx * 8);
+    constexpr int NONE = LINE ? (int)PIX_NONE : -1;  // a voxel outside the image
     float pc[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -823,19 +843,51 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
         const float nu = pc[0] * p.fx, nv = pc[1] * p.fy;
         // Certified fast projection.  Only floor(u), floor(v) and the bound tests are used, so u = nu * rcp(z) decides
         // them exactly unless u lies within proj_eps of an integer (the bound tests 0.0001 and W - 0.0001 sit 1e-4
-        // from integers); those rare waves redo the IEEE quotients.
+        // from integers); those rare lanes redo the IEEE quotients.  A NaN fails the > and is not certified.
         const float rz = __builtin_amdgcn_rcpf(pc[2]);
         float u_f = (nu * rz + p.cx) + 0.5f;
         float v_f = (nv * rz + p.cy) + 0.5f;
-        const bool sure = !(pc[2] > 0.0f) || ((int)(fabsf(u_f - __builtin_rintf(u_f)) > p.proj_eps) &
-                                              (int)(fabsf(v_f - __builtin_rintf(v_f)) > p.proj_eps));
-        if (!sure) {
-            u_f = ((nu / pc[2]) + p.cx) + 0.5f;
-            v_f = ((nv / pc[2]) + p.cy) + 0.5f;
+        if constexpr (LINE) {
+            // Select form: every lane computes the mask of unsure lanes (no exec region around the rint and compare
+            // steps), and the wave branches once, uniformly and seldom (0.17 % of the voxel visits are unsure at
+            // 640 x 480, a tenth of a wave's voxel steps), to the exact block, which is laid out of line.  The block
+            // serves this voxel step alone: merged over the wave's ZB steps it would run on a third of the wave-frames.
+            const bool front = pc[2] > 0.0f;
+            const bool cert = (int)(fabsf(u_f - __builtin_rintf(u_f)) > p.proj_eps) &
+                              (int)(fabsf(v_f - __builtin_rintf(v_f)) > p.proj_eps);
+            const bool unsure = front & !cert;
+            // Bounds of a certified lane from its integer pixel.  Its u_f is farther than proj_eps from every integer
+            // (so |u_f| < 2^23; infinities and NaN fail the compare), and proj_eps > 1.2e-4 + 2^-21 max(W, H) exceeds
+            // both of Open3D's margins: 1e-4, and W - safe_w <= 1e-4 + ulp(W) / 2 <= 1e-4 + 2^-24 W (safe_w is
+            // W - 1e-4 rounded to float).  So u_f lies neither in [0, 1e-4) nor in [safe_w, W), and
+            //   u_f >= 0.0001f && u_f < safe_w  <=>  0 <= floor(u_f) < W  <=>  (unsigned)floor(u_f) < W,
+            // likewise v_f and H; and the certification itself says that the exact u takes the same floor and the same
+            // side of both bounds.  An unsure lane's pixel from this test is replaced below; behind the camera front
+            // is false whatever the conversions gave.
+            const int ui = floor_to_int(u_f), vi = floor_to_int(v_f);
+            const bool ok = front & ((unsigned)ui < (unsigned)p.W) & ((unsigned)vi < (unsigned)p.H);
+            int pix = ok ? (int)__umul24((unsigned)vi, (unsigned)p.W) + ui : NONE;
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(unsure) != 0ull, 0)) {
+                // the exact quotients take Open3D's own tests: there the slivers [0, 1e-4) and [W - 1e-4, W), which
+                // floor() would place inside, are outside
+                const float ue = ((nu / pc[2]) + p.cx) + 0.5f;
+                const float ve = ((nv / pc[2]) + p.cy) + 0.5f;
+                const bool oke = (ue >= 0.0001f) & (ue < p.safe_w) & (ve >= 0.0001f) & (ve < p.safe_h);
+                const int pe = oke ? (int)__umul24((unsigned)(int)ve, (unsigned)p.W) + (int)ue : NONE;
+                pix = unsure ? pe : pix;
+            }
+            pixv[k] = pix;
+        } else {
+            const bool sure = !(pc[2] > 0.0f) || ((int)(fabsf(u_f - __builtin_rintf(u_f)) > p.proj_eps) &
+                                                  (int)(fabsf(v_f - __builtin_rintf(v_f)) > p.proj_eps));
+            if (!sure) {
+                u_f = ((nu / pc[2]) + p.cx) + 0.5f;
+                v_f = ((nv / pc[2]) + p.cy) + 0.5f;
+            }
+            // non-short-circuit test keeps all ZB projections in one basic block
+            const bool ok = (pc[2] > 0.0f) & (u_f >= 0.0001f) & (u_f < p.safe_w) & (v_f >= 0.0001f) & (v_f < p.safe_h);
+            pixv[k] = ok ? (int)__umul24((unsigned)(int)v_f, (unsigned)p.W) + (int)u_f : NONE;
         }
-        // non-short-circuit test keeps all ZB projections in one basic block
-        const bool ok = (pc[2] > 0.0f) & (u_f >= 0.0001f) & (u_f < p.safe_w) & (v_f >= 0.0001f) & (v_f < p.safe_h);
-        pixv[k] = ok ? (int)__umul24((unsigned)(int)v_f, (unsigned)p.W) + (int)u_f : -1;
         pcz[k] = pc[2];
         pc[0] += es0;
         pc[1] += es1;
@@ -845,12 +897,19 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
     // 64-bit address math)
 #pragma unroll
     for (int k = 0; k < ZB; ++k) {
-        dv[k] = 0.0f;
-        cv[k] = 0u;
-        if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
-            const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, pixv[k] * 8, 0, 0);
+        if constexpr (LINE) {
+            // every lane loads, back to back; a voxel outside the image carries PIX_NONE: depth 0, colour 0
+            const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, (int)((unsigned)pixv[k] * 8u), 0, 0);
             dv[k] = __uint_as_float(raw.x);
             cv[k] = raw.y;
+        } else {
+            dv[k] = 0.0f;
+            cv[k] = 0u;
+            if (pixv[k] >= 0) {  // lanes projecting outside the image issue no gather
+                const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(dc_rsrc, pixv[k] * 8, 0, 0);
+                dv[k] = __uint_as_float(raw.x);
+                cv[k] = raw.y;
+            }
         }
     }
 }
@@ -860,17 +919,19 @@ __device__ __forceinline__ void frame_tap(const BatchFrame& fr, const IntegrateP
 // superset of the updating lanes and needs no m; the update's test on the product is then Open3D's.  A frame none of
 // whose lanes is a candidate for any of the wave's voxels ends there for a coarse wave (integrate_frames): cand false
 // already meant "select the old value" on every lane, so nothing after the test can change a voxel, the update count
-// or the write-back decision.
+// or the write-back decision.  LINE (frame_tap's): a voxel outside the image gathered depth 0 and fails dv > 0 by itself.
+template <bool LINE>
 __device__ __forceinline__ bool voxel_candidate(const IntegrateParams& p, int pix, float pcz, float dv, float& df) {
     df = dv - pcz;
-    return (pix >= 0) & (dv > 0.0f) & (df > -p.trunc);
+    if constexpr (LINE) return (dv > 0.0f) & (df > -p.trunc);
+    else return (pix >= 0) & (dv > 0.0f) & (df > -p.trunc);
 }
 // The multiplier gather (the volume's one table, not a per-frame copy), by the candidate lanes only: the gathered
 // multiplier's float bits on the candidate lanes.  On the other lanes the result is not a multiplier -- SHARE (the
 // coarse loop): the gather's byte offset, offset and result in one register, which the 64-VGPR float64-colour kernel
 // needs; !SHARE (the fine pipeline's slots, 3-4 % faster per launch so): zero -- so df * mv may be anything there, NaN
 // included; cand is false on those lanes and voxel_update only selects.  Use mv or the product outside a select on
-// cand nowhere.
+// cand nowhere.  (A gather by every lane, the others from past the end of the table, measured no gain: DESIGN.md §4.3.)
 template <bool SHARE>
 __device__ __forceinline__ unsigned voxel_multiplier(const __amdgpu_buffer_rsrc_t& mult_rsrc, int pix, bool cand) {
     unsigned mv = SHARE ? (unsigned)pix * 4u : 0u;
@@ -962,10 +1023,10 @@ __device__ __forceinline__ void integrate_frames(const BatchFrame* __restrict__ 
         uint32_t cv[ZB];
         bool cand[ZB];
         unsigned mv[ZB];
-        frame_tap<ZB>(fr, p, npx, fpx, fpy, fpz, z0, pixv, pcz, dv, cv);
+        frame_tap<ZB, true>(fr, p, npx, fpx, fpy, fpz, z0, pixv, pcz, dv, cv);
         bool some = false;
 #pragma unroll
-        for (int k = 0; k < ZB; ++k) some |= cand[k] = voxel_candidate(p, pixv[k], pcz[k], dv[k], df[k]);
+        for (int k = 0; k < ZB; ++k) some |= cand[k] = voxel_candidate<true>(p, pixv[k], pcz[k], dv[k], df[k]);
         // an idle wave-frame (no candidate lane: the surface is elsewhere in this frame, or its depth is missing) leaves
         // before the multiplier gathers, the reciprocal reads and the updates -- the loop's one new uniform branch, a
         // scalar compare of the lane mask
@@ -1063,7 +1124,7 @@ __device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ fr
                 const int f = __ffsll((long long)mt) - 1;
                 mt &= mt - 1;
                 fs[j] = f;
-                frame_tap<ZB>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
+                frame_tap<ZB, false>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
             } else {
                 fs[j] = -1;
             }
@@ -1074,7 +1135,7 @@ __device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ fr
             const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
 #pragma unroll
             for (int k = 0; k < ZB; ++k) {  // test and gather voxel by voxel: no frame is left early here
-                cand[j][k] = voxel_candidate(p, pixv[j][k], pcz[j][k], dv[j][k], df[j][k]);
+                cand[j][k] = voxel_candidate<false>(p, pixv[j][k], pcz[j][k], dv[j][k], df[j][k]);
                 mv[j][k] = voxel_multiplier<false>(mult_rsrc, pixv[j][k], cand[j][k]);
             }
         };
@@ -1621,6 +1682,9 @@ static ot_status check_frame(const ot_tsdf* vol, const void* depth, const uint8_
     if (!depth || !in || !ext || in->width <= 0 || in->height <= 0 ||
         (vol->color_type == OT_COLOR_RGB8 && !color))
         return fail(OT_ERR_UNSUPPORTED_FORMAT, "[ScalableTSDFVolume::Integrate] Unsupported image format.");
+    // the integrate's gathers address a frame by 32-bit byte offsets and send the voxels outside it to pixel PIX_NONE
+    if ((int64_t)in->width * in->height >= (int64_t)PIX_NONE)
+        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume::Integrate] image of 2^28 pixels or more");
     return OT_OK;
 }
 
