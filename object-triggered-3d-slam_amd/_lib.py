@@ -148,6 +148,7 @@ TEST_SIGNATURES = {
     "otx_unit_sort_radix": [_i32],
     "otx_sor_netfill": [_i32],
     "otx_integrate_fine": [_i32],
+    "otx_integrate_workgroup": [_i32],
     "otx_touch_stage_blocks": [_i32],
     "otx_touch_frames": [_i32],
     "otx_split_frontend": [_i32],

@@ -450,10 +450,11 @@ __global__ __launch_bounds__(256) void k_batch_touch_split(const BatchFrame* __r
 // unit header (id, key, frame mask) is resolved once by k_batch_units and read with scalar loads.
 constexpr int BZ = 4;                         // voxels per lane along z (2: slower, profiles/r03w_*)
 constexpr int SLICES = 4 * (UNIT_RES / BZ);   // waves per unit
-// waves per integrate workgroup: a quarter unit (measured per 32-frame launch, float64 colour: 16 waves 0.511 ms,
-// 8 waves 0.452 ms, 4 waves 0.426 ms; float32 colour 0.402 / 0.383 / 0.378)
+// waves per workgroup of the fine and the fused integrates, and the unit of the coarse / fine rules: a quarter unit
+// (measured per 32-frame launch, float64 colour: 16 waves 0.511 ms, 8 waves 0.452 ms, 4 waves 0.426 ms; float32 colour
+// 0.402 / 0.383 / 0.378).  The coarse launch of its own goes down to one wave (integrate_form).
 constexpr int INT_WG = 4;
-constexpr int INT_PARTS = SLICES / INT_WG;  // workgroups per unit
+constexpr int INT_PARTS = SLICES / INT_WG;  // four-wave workgroups per unit
 
 struct UnitWork {
     int id;                   // pool id, | 0x80000000 when fresh (state starts at zero), -1 when dropped
@@ -790,7 +791,8 @@ constexpr int INT_WAVES_PER_EU = 8;
 // mean and a term quantised by the depth / camera-distance floats; colour: c*w + rgb >= 0 with c a mean of bytes).
 // Otherwise the IEEE divisions (FAST = false: tests/test_gpu_tsdf.py::test_long_scan_crosses_reciprocal_table and
 // ::test_ieee_division_kernel_after_import run both across the switch).
-constexpr int RCP_N = 2048;  // 16 KiB (float64) / 8 KiB (float32) of LDS per workgroup: 8 quarter-unit workgroups per CU
+constexpr int RCP_N = 2048;  // at most 16 KiB (float64) / 8 KiB (float32) of LDS per workgroup (the table's first
+                             // rcp_hi entries: integrate_form sizes the launch's dynamic LDS to the batch)
 
 // Phases A and B of one frame for a lane's ZB voxels at column position (px, py, pz), slice start z0: the certified
 // projections and the (depth, colour) gathers.  No voxel state is read, so the fine slices' frame pipeline issues them
@@ -1190,10 +1192,14 @@ __device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ fr
     }
 }
 
-// One workgroup of INT_WG waves per unit part (a quarter unit by default: small workgroups let the CU keep 6-8 of them
-// resident instead of one 16-wave unit -- a unit-sized workgroup left the float64-colour kernel at 4 waves per SIMD
-// whatever its registers); the parts of a unit run on one XCD.  Work items are assigned by a static grid stride that
-// every wave derives on its own: no atomics, one barrier (the reciprocal table).
+// One workgroup of WG waves per unit part.  The waves of a workgroup never meet after the table's barrier, but the
+// workgroup keeps its place on the CU until its slowest wave ends, and a wave behind the surface leaves every frame at
+// the idle-frame branch while its neighbour does not: the smaller the workgroup, the sooner a finished wave's slot is
+// refilled.  The product's coarse launch has one wave per workgroup (a sixteenth of a unit; integrate_form), the fine
+// slices and the fused launches INT_WG (a quarter unit at BZ).  Per launch of the headline scan, 16 / 8 / 4 waves: 0.511
+// / 0.452 / 0.426 ms (round 3); 4 / 2 / 1 waves: DESIGN.md §4.1.  The parts of a unit run on one XCD.  Work items are
+// assigned by a static grid stride that every wave derives on its own: no atomics, and one barrier (the reciprocal
+// table) where the workgroup has more than one wave.
 // C64: colour state in float64 (Open3D's TSDFVoxel::color_ is Eigen::Vector3d), in the record's float64 planes.
 // one table per kernel: float64 reciprocals for the float64-colour kernel (its float32 ones are their roundings:
 // (float)RN64(1/n) == RN32(1/n) for every n <= 2^20, no double-rounding case -- tools/markstein_check.cpp), float32
@@ -1207,9 +1213,9 @@ struct RcpLds {
 // the integrate half of k_integrate_touch / k_integrate_touch_fine.  Everything per item is shared (integrate_item: the
 // record's load and store, the frame loops, the tap, the candidate stage, the per-voxel update, each written once
 // above); the callers differ in three things only, all passed in: the workgroup's id and count (blockIdx.x /
-// gridDim.x against the fused launch's split of the grid), the home of the reciprocal table (s_r32 / s_r64: static
-// __shared__ arrays against a member of the fused kernels' LDS union) and the work-list index (HEAVY: the fused
-// launch walks heavy units first, the rest back to front -- k_batch_units).
+// gridDim.x against the fused launch's split of the grid), the home of the reciprocal table (s_r32 / s_r64: the
+// launch's dynamic LDS, sized to the batch, against a member of the fused kernels' LDS union) and the work-list index
+// (HEAVY: the fused launch walks heavy units first, the rest back to front -- k_batch_units).  WG: waves per workgroup.
 // Decision and measurements: DESIGN.md §4.2.
 //
 // work item = (unit, part): the PARTS parts of a unit are items 8 apart, so they run on one XCD (blocks are dealt
@@ -1217,22 +1223,24 @@ struct RcpLds {
 // The grid is sized for large batches (8x the resident workgroups): a workgroup without an item leaves before
 // building the reciprocal table -- for a batch of few units (a spatial shard) the idle workgroups' tables had cost
 // more than the integrate itself (r05e: a 1/8 shard's 64-frame batch 165-200 us whatever its slicing)
-template <bool C64, bool FAST, int ZB, int KT, bool HEAVY>
+template <bool C64, bool FAST, int ZB, int KT, bool HEAVY, int WG>
 __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ frames, const IntegrateParams& p,
                                                const TsdfDev& d, const UnitWork* __restrict__ work,
                                                const int* __restrict__ wcount, float* s_r32, double* s_r64, int bid,
                                                int nblk) {
-    constexpr int PARTS = 4 * (UNIT_RES / ZB) / INT_WG;  // workgroups per unit (INT_PARTS at the default ZB)
+    constexpr int PARTS = 4 * (UNIT_RES / ZB) / WG;  // workgroups per unit
     {
         const int n0 = __builtin_amdgcn_readfirstlane(__hip_atomic_load(wcount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         if (bid >= (PARTS == 1 ? n0 : ((n0 + 7) / 8) * 8 * PARTS)) return;
     }
     if constexpr (FAST) {
-        for (int r = 1 + threadIdx.x; r <= p.rcp_hi; r += 64 * INT_WG) {  // entries 1 .. the batch's largest weight + 1
+        for (int r = 1 + threadIdx.x; r <= p.rcp_hi; r += 64 * WG) {  // entries 1 .. the batch's largest weight + 1
             if constexpr (C64) s_r64[r] = 1.0 / (double)r;  // IEEE (correctly rounded) quotients
             else s_r32[r] = 1.0f / (float)r;
         }
-        __syncthreads();
+        // a single wave's LDS operations complete in order: it needs no barrier to read what its own lanes wrote
+        if constexpr (WG > 1) __syncthreads();
+        else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // once, in a scalar register
     const int n = *wcount;
@@ -1244,7 +1252,7 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
         const int u = PARTS == 1 ? it : (it / (8 * PARTS)) * 8 + (it & 7);
         if (PARTS > 1 && u >= n) continue;
         const int part = PARTS == 1 ? 0 : (it >> 3) % PARTS;
-        const int s = part * INT_WG + wave;  // slice of this wave
+        const int s = part * WG + wave;  // slice of this wave
         integrate_item<C64, FAST, ZB, KT>(frames, p, d, work[!HEAVY || u < nh ? u : n - 1 - (u - nh)], s, npx, s_r32,
                                           s_r64, upd);
     }
@@ -1252,14 +1260,16 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
     if ((threadIdx.x & 63) == 0 && tot) atomicAdd(&d.stats[S_UPDATES], tot);
 }
 
-// the integrate of a batch as a launch of its own (the product kernel: <C64, FAST, BZ, 1>; ZB == 2: fine slices)
-template <bool C64, bool FAST, int ZB = BZ, int KT = 1>
-__global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : INT_WAVES_PER_EU)) void k_batch_integrate(
+// the integrate of a batch as a launch of its own (the product kernel: <C64, FAST, BZ, 1, 1>; ZB == 2: fine slices).
+// The reciprocal table is the launch's dynamic LDS: rcp_hi + 1 entries of the kernel's precision (integrate_form), so a
+// CU holds as many one-wave workgroups as it has wave slots until the table passes 5 KiB.
+extern __shared__ double s_rcp_dyn[];
+template <bool C64, bool FAST, int ZB = BZ, int KT = 1, int WG = INT_WG>
+__global__ __launch_bounds__(64 * WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : INT_WAVES_PER_EU)) void k_batch_integrate(
     const BatchFrame* __restrict__ frames, IntegrateParams p, TsdfDev d, const UnitWork* __restrict__ work,
     const int* __restrict__ wcount) {
-    __shared__ float s_r32[(FAST && !C64) ? RCP_N + 1 : 1];
-    __shared__ double s_r64[(FAST && C64) ? RCP_N + 1 : 1];
-    integrate_body<C64, FAST, ZB, KT, false>(frames, p, d, work, wcount, s_r32, s_r64, (int)blockIdx.x, (int)gridDim.x);
+    integrate_body<C64, FAST, ZB, KT, false, WG>(frames, p, d, work, wcount, reinterpret_cast<float*>(s_rcp_dyn),
+                                                 s_rcp_dyn, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The deferred integrate of a sharded volume's batch k and the touch of batch k + 1 in ONE launch (round 6): workgroups
@@ -1282,7 +1292,7 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : INT_WAVES_PER_EU)
     __shared__ Lds lds;
     const int b = (int)blockIdx.x;
     if (b < nint) {
-        integrate_body<C64, FAST, BZ, 1, true>(frames, p, d, work, wcount, lds.r.r32, lds.r.r64, b, nint);
+        integrate_body<C64, FAST, BZ, 1, true, INT_WG>(frames, p, d, work, wcount, lds.r.r32, lds.r.r64, b, nint);
     } else {
         const int t = b - nint;
         touch_body<false, false>(tframes, tp, d, tn, lds.t, t % tp.tiles, t / tp.tiles);
@@ -1302,7 +1312,7 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : 4) void k_integra
     __shared__ Lds lds;
     const int b = (int)blockIdx.x;
     if (b < nint) {
-        integrate_body<C64, FAST, 2, 1, true>(frames, p, d, work, wcount, lds.r.r32, lds.r.r64, b, nint);
+        integrate_body<C64, FAST, 2, 1, true, INT_WG>(frames, p, d, work, wcount, lds.r.r32, lds.r.r64, b, nint);
     } else {
         const int t = b - nint;
         touch_body<false, false>(tframes, tp, d, tn, lds.t, t % tp.tiles, t / tp.tiles);
@@ -1688,10 +1698,11 @@ static ot_status check_frame(const ot_tsdf* vol, const void* depth, const uint8_
     return OT_OK;
 }
 
-// Grid of k_batch_integrate: INT_GRID_MULT x the co-resident workgroups (cached per device and kernel; a benign race at
-// worst computes the same value twice).  A 64-frame batch of the configs[1] scan has ~12k (unit, quarter) items: at 8x
-// (16k workgroups) nearly every workgroup takes one item and the dispatcher balances them; at 4x some take two in a
-// static stride (0.77 vs 0.72 ms per launch; 6x / 12x / 16x / 32x: within 2 %, slower).
+// Grid of k_batch_integrate: INT_GRID_MULT x the co-resident workgroups (integrate_resident).  Measured with four-wave
+// workgroups: a 64-frame batch of the configs[1] scan has ~12k (unit, quarter) items; at 8x (16k workgroups) nearly
+// every workgroup takes one item and the dispatcher balances them; at 4x some take two in a static stride (0.77 vs
+// 0.72 ms per launch; 6x / 12x / 16x / 32x: within 2 %, slower).  One-wave workgroups keep the ratio: 64k workgroups
+// for the headline batch's 60k (unit, slice) items.
 constexpr int INT_GRID_MULT = 8;
 
 // the integrate instantiation of a batch: colour precision 64 (bit 1), reciprocal table (bit 0), fine slices (bit 2:
@@ -1703,10 +1714,21 @@ static int g_stage_blocks = -1;  // test hook otx_touch_stage_blocks: staging-on
 // bits 3-4 of a fine variant: the frame pipeline's depth KT - 1 (k_batch_integrate's ZB == 2 loop)
 static int g_int_depth = -1;  // test hook otx_integrate_depth: -1 the default (INT_FINE_KT), else KT in 1..3
 constexpr int INT_FINE_KT = 1;
-static const void* integrate_kernel(int variant) {
-    static const void* const k[20] = {
-        (const void*)k_batch_integrate<false, false>, (const void*)k_batch_integrate<false, true>,
-        (const void*)k_batch_integrate<true, false>, (const void*)k_batch_integrate<true, true>,
+// Waves per workgroup of the coarse integrate: a finished wave frees its wave slot at once, but its
+// workgroup's place on the CU only when the slowest wave ends, so the smaller the workgroup the sooner the dispatcher
+// refills the slot.  The fine slices and the fused launches keep INT_WG waves.
+constexpr int INT_WG_DEFAULT = 1;
+static int g_int_wg = -1;  // test hook otx_integrate_workgroup: -1 the default rule (integrate_form), else 1, 2 or 4
+template <int WG>
+static const void* coarse_kernel(int variant) {
+    static const void* const k[4] = {
+        (const void*)k_batch_integrate<false, false, BZ, 1, WG>, (const void*)k_batch_integrate<false, true, BZ, 1, WG>,
+        (const void*)k_batch_integrate<true, false, BZ, 1, WG>, (const void*)k_batch_integrate<true, true, BZ, 1, WG>};
+    return k[variant & 3];
+}
+// wg: waves per workgroup of a coarse variant (1, 2 or 4); the fine variants have INT_WG
+static const void* integrate_kernel(int variant, int wg) {
+    static const void* const k[16] = {
         (const void*)k_batch_integrate<false, false, 2, 1>, (const void*)k_batch_integrate<false, true, 2, 1>,
         (const void*)k_batch_integrate<true, false, 2, 1>, (const void*)k_batch_integrate<true, true, 2, 1>,
         nullptr, nullptr, nullptr, nullptr,
@@ -1716,25 +1738,72 @@ static const void* integrate_kernel(int variant) {
     static const void* const k3[4] = {
         (const void*)k_batch_integrate<false, false, 2, 3>, (const void*)k_batch_integrate<false, true, 2, 3>,
         (const void*)k_batch_integrate<true, false, 2, 3>, (const void*)k_batch_integrate<true, true, 2, 3>};
-    if ((variant & 4) && ((variant >> 3) & 3) == 2) return k3[variant & 3];
-    return k[(variant & 4) ? (variant & 7) + 8 * ((variant >> 3) & 1) : (variant & 3)];
+    if (!(variant & 4))
+        return wg == 1 ? coarse_kernel<1>(variant) : wg == 2 ? coarse_kernel<2>(variant) : coarse_kernel<4>(variant);
+    if (((variant >> 3) & 3) == 2) return k3[variant & 3];
+    return k[(variant & 3) + 8 * ((variant >> 3) & 1)];
 }
 
-static int integrate_grid(int variant) {
-    static int cache[32][64] = {{0}};
+// LDS of a launch: the table's entries 0 .. rcp_hi in the variant's precision (the hardware allocates whole granules)
+constexpr unsigned LDS_GRANULE = 1280;
+constexpr unsigned RCP_LDS_MAX = ((RCP_N + 1) * 8 + LDS_GRANULE - 1) / LDS_GRANULE;  // in granules
+static unsigned rcp_lds_bytes(int variant, int rcp_hi) {
+    if (!(variant & 1)) return 0;  // IEEE divisions: no table
+    const unsigned bytes = (unsigned)(std::min(std::max(rcp_hi, 1), RCP_N) + 1) * ((variant & 2) ? 8u : 4u);
+    return (bytes + 15u) & ~15u;
+}
+
+// Co-resident workgroups of an integrate kernel on the device, by its waves per workgroup and its dynamic LDS in whole
+// granules (cached per device, kernel and size; a benign race at worst computes the same value twice).  0: the query
+// failed.
+static int integrate_resident(int variant, int wg, unsigned lds) {
+    static int cache[32][3][RCP_LDS_MAX + 1][64] = {};
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 4096;
-    int* cache_c = cache[variant & 31];
-    if (!cache_c[dev]) {
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    const unsigned granules = std::min((lds + LDS_GRANULE - 1) / LDS_GRANULE, RCP_LDS_MAX);
+    int* c = &cache[variant & 31][wg == 1 ? 0 : wg == 2 ? 1 : 2][granules][dev];
+    if (!*c) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, integrate_kernel(variant), 64 * INT_WG, 0) !=
-                hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, integrate_kernel(variant, wg), 64 * wg,
+                                                         granules * LDS_GRANULE) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu <= 0 ||
             cus <= 0)
-            return 4096;
-        cache_c[dev] = per_cu * cus * INT_GRID_MULT;
+            return 0;
+        *c = per_cu * cus;
     }
-    return cache_c[dev];
+    return *c;
+}
+
+// Grid of a four-wave integrate with the whole table: INT_GRID_MULT x its co-resident workgroups.  The unit of the
+// rules that choose between coarse and fine slices, and the integrate's share of a fused launch.
+static int integrate_grid(int variant) {
+    const int r = integrate_resident(variant, INT_WG, rcp_lds_bytes(variant, RCP_N));
+    return r ? r * INT_GRID_MULT : 4096;
+}
+
+// The launch of k_batch_integrate for a batch: kernel, waves per workgroup, dynamic LDS and grid.  A coarse variant takes
+// the smallest workgroup from the default up that keeps as many waves resident as four-wave workgroups would: the
+// table's LDS bounds the workgroups per CU, so late in a long scan (rcp_hi towards RCP_N) one-wave workgroups would
+// leave wave slots empty and the launch falls back to two and four waves.  The grid stays INT_GRID_MULT x the resident
+// workgroups, so a headline batch's (unit, slice) items get one workgroup each.
+struct IntForm {
+    const void* fn;
+    int wg, grid;
+    unsigned lds;
+};
+static IntForm integrate_form(int variant, int rcp_hi) {
+    IntForm f;
+    f.lds = rcp_lds_bytes(variant, rcp_hi);
+    f.wg = INT_WG;
+    if (!(variant & 4)) {
+        const int want = integrate_resident(variant, INT_WG, f.lds) * INT_WG;  // waves
+        f.wg = g_int_wg > 0 ? g_int_wg : INT_WG_DEFAULT;
+        while (g_int_wg <= 0 && f.wg < INT_WG && integrate_resident(variant, f.wg, f.lds) * f.wg < want) f.wg *= 2;
+    }
+    f.fn = integrate_kernel(variant, f.wg);
+    const int r = integrate_resident(variant, f.wg, f.lds);
+    f.grid = r ? r * INT_GRID_MULT : 4096 * (INT_WG / f.wg);
+    return f;
 }
 
 // the context a batch's settle (and a replay) needs
@@ -1883,7 +1952,8 @@ static ot_status launch_deferred(ot_tsdf* vol, hipStream_t stream, const BatchCt
         OT_HIP_TRY(hipLaunchKernel(kt[(variant & 3) + (fine ? 4 : 0)], dim3(grid), dim3(64 * INT_WG), args, 0, stream));
     } else {
         void* args[] = {(void*)&bf, (void*)&D.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wc};
-        OT_HIP_TRY(hipLaunchKernel(integrate_kernel(variant), dim3(nint), dim3(64 * INT_WG), args, 0, stream));
+        const IntForm f = integrate_form(variant, D.ip0.rcp_hi);
+        OT_HIP_TRY(hipLaunchKernel(f.fn, dim3(f.grid), dim3(64 * f.wg), args, f.lds, stream));
     }
     OT_LAUNCH_CHECK();
     if (vol->profiling) {
@@ -2060,7 +2130,7 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
         vol->early_frame = vol->frame_id;
         return settle_batch(vol, bc, stream);
     }
-    const int grid = integrate_grid(bc.variant);
+    const IntForm form = integrate_form(bc.variant, bc.ip0.rcp_hi);
     // overlap: the integrate on istream behind this set's units kernel (and the previous batch's integrate: same
     // stream), so the caller's stream is free for the next batch's front end
     hipStream_t is = stream;
@@ -2081,7 +2151,7 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
     const UnitWork* uw = work;
     const int* wc = wcount;
     void* args[] = {(void*)&bf, (void*)&bc.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wc};
-    OT_HIP_TRY(hipLaunchKernel(integrate_kernel(bc.variant), dim3(grid), dim3(64 * INT_WG), args, 0, is));
+    OT_HIP_TRY(hipLaunchKernel(form.fn, dim3(form.grid), dim3(64 * form.wg), args, form.lds, is));
     vol->batch_pc ^= 1;  // only once this batch's kernels are queued (its units kernel zeroes the other counter)
     OT_LAUNCH_CHECK();
     if (vol->profiling) {
@@ -2240,8 +2310,8 @@ static ot_status settle_batch(ot_tsdf* vol, const BatchCtx& bc, hipStream_t stre
         const UnitWork* uw = work;
         const int* wc = vol->dev.counters + bc.pc;
         void* args[] = {(void*)&bf, (void*)&bc.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wc};
-        OT_HIP_TRY(hipLaunchKernel(integrate_kernel(bc.variant), dim3(integrate_grid(bc.variant)), dim3(64 * INT_WG),
-                                   args, 0, stream));
+        const IntForm f = integrate_form(bc.variant, bc.ip0.rcp_hi);
+        OT_HIP_TRY(hipLaunchKernel(f.fn, dim3(f.grid), dim3(64 * f.wg), args, f.lds, stream));
         OT_LAUNCH_CHECK();
         vol->last_set = -1;  // the replay ran on the caller's stream, after both streams drained
         vol->sorted_frame = -1;
@@ -2839,6 +2909,15 @@ ot_status otx_tsdf_stats(ot_tsdf* vol, uint64_t* out4) {
 ot_status otx_integrate_fine(int32_t mode) {
     g_int_fine = mode < 0 ? -1 : (mode == 1 ? 1 : 0);
     g_fine_units = mode >= 2 ? mode : -1;
+    return OT_OK;
+}
+
+// test hook: waves per workgroup of the coarse integrate (-1 = the default rule of integrate_form; 1, 2 or 4 forced at
+// every table size): A/B timing and the parity of the three forms
+ot_status otx_integrate_workgroup(int32_t waves) {
+    if (waves != -1 && waves != 1 && waves != 2 && waves != 4)
+        return fail(OT_ERR_INVALID_ARGUMENT, "otx_integrate_workgroup: -1, 1, 2 or 4 waves");
+    g_int_wg = waves;
     return OT_OK;
 }
 
