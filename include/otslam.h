@@ -501,6 +501,95 @@ ot_status ot_change_grid_update(ot_change_grid* grid, const int32_t* keys_host, 
 ot_status ot_change_grid_publish(const ot_change_grid* grid, float* out_xyz_host, int64_t capacity,
                                  int64_t* n_host);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Object trigger: scan clustering, object map filter, goal observations (DESIGN.md §4 "scan clustering")
+ * ------------------------------------------------------------------------------------------------- */
+
+/* The parameters of LidarClusterPublisher (lidar_cluster_publisher.cpp:73-102) with the node's defaults
+ * 0.2, 1, 1.0, 1.0, 2.0, 0.001, 1, 20; held as float / int as the node's members are. */
+typedef struct ot_scan_cluster_params {
+    float gap_threshold;
+    int32_t min_cluster_points;
+    float max_range_ratio;
+    float obj_len_max;
+    float wal_len_min;
+    float wal_lin_max;
+    int32_t obj_nmp_min;
+    int32_t wal_nmp_min;
+} ot_scan_cluster_params;
+
+#define OT_SCAN_CLASS_NONE 0
+#define OT_SCAN_CLASS_WALL 1
+#define OT_SCAN_CLASS_OBJECT 2
+#define OT_SCAN_CLASS_UNKNOWN 3
+#define OT_SCAN_CLUSTER_MAX_BEAMS 4096
+
+/* one row of the cluster table (24 bytes) */
+typedef struct ot_scan_cluster_row {
+    int32_t first_beam; /* beam of the cluster's first stored point (seam-merged: the last cluster's first) */
+    int32_t n_points;
+    float length;  /* bounding-box diagonal, float as the node */
+    int32_t cls;   /* OT_SCAN_CLASS_* */
+    double linearity; /* float64 definition of DESIGN.md §4 */
+} ot_scan_cluster_row;
+
+/* lidar_cluster_publisher.cpp:151-291 LidarClusterPublisher::scanCallback, batched over n_scans scans of device
+ * float ranges [n_scans][n_beams], 0 < n_beams <= OT_SCAN_CLUSTER_MAX_BEAMS (one workgroup stages a scan in LDS;
+ * more beams -> OT_ERR_INVALID_ARGUMENT).  A beam is valid when finite and <= range_max * max_range_ratio
+ * (:162-163); consecutive valid beams further apart than gap_threshold (hypotf, :172-173) start a new cluster;
+ * clusters below min_cluster_points are dropped (:175, :182); the last and first kept clusters merge across the
+ * seam when their end points are closer than gap_threshold (:186-199; a single kept cluster is kept once — the
+ * node's self-insert is undefined); each cluster is WALL / OBJECT / UNKNOWN by :245-256 from its float length,
+ * its linearity (float64 definition) and its point count.  min_cluster_points < 1 is refused (with 0
+ * the node pushes an empty cluster for a scan without valid beams).  poses_host [n_scans][7] = (tx, ty, tz,
+ * qx, qy, qz, qw) map <- base_link, NULL = identity.  Device outputs: beam_cluster int32 [n_scans][n_beams]
+ * (index in the node's final cluster list, -1 = none), beam_class uint8 (OT_SCAN_CLASS_*), beam_xy float32
+ * [n_scans][n_beams][2] (map frame, :265-274: the double transform cast to float; NaN for invalid beams),
+ * n_clusters int32 [n_scans], clusters [n_scans][n_beams] rows (the first n_clusters of a scan are written).
+ * The three published clouds (:287-290), float32 xyz with z = 0, are written concatenated over scans in the
+ * node's order (cluster-list order, stored order inside a cluster) into wall_xyz / object_xyz / unknown_xyz
+ * (capacity n_scans * n_beams rows each); cloud_offsets_host int64 [3][n_scans + 1] (wall, object, unknown)
+ * receives their per-scan row offsets. */
+ot_status ot_scan_cluster(const float* ranges, int32_t n_scans, int32_t n_beams, float angle_min,
+                          float angle_increment, float range_max, const double* poses_host,
+                          const ot_scan_cluster_params* params, int32_t* beam_cluster, uint8_t* beam_class,
+                          float* beam_xy, int32_t* n_clusters, ot_scan_cluster_row* clusters, float* wall_xyz,
+                          float* object_xyz, float* unknown_xyz, int64_t* cloud_offsets_host, void* stream);
+
+/* object_filter.cpp:51-155 ObjectMapFilter, batched: object points float32 xyz, concatenated, scan s = rows
+ * [offsets_host[s], offsets_host[s+1]).  The wall points of scan s come from virtual_ranges[s] (device float
+ * [n_scans][n_beams]; NaN, inf and r > range_max skipped, :66), moved to the map frame by the yaw of
+ * poses_host[s] (:157-172; NULL = identity).  A point is kept when no wall point lies closer than
+ * proximity_threshold (:120-127: float differences and squares, compared in double); a scan without wall
+ * points keeps nothing (:93).  keep_mask uint8 [n_points]; out_xyz the kept points in input order (capacity
+ * n_points rows); out_offsets_host int64 [n_scans + 1] their per-scan offsets. */
+ot_status ot_object_map_filter(const float* object_xyz, const int64_t* offsets_host, int32_t n_scans,
+                               const float* virtual_ranges, int32_t n_beams, float angle_min, float angle_increment,
+                               float range_max, const double* poses_host, double proximity_threshold,
+                               uint8_t* keep_mask, float* out_xyz, int64_t* out_offsets_host, void* stream);
+
+/* The parameters of the goal selector's clustering (3_multi_object_goal_selector.cpp:41-45), defaults 0.4, 10,
+ * 0.2, 0.5. */
+typedef struct ot_observation_params {
+    double cluster_distance_threshold;
+    double wall_thickness_threshold;
+    double lock_margin;
+    int32_t min_cluster_points;
+} ot_observation_params;
+
+/* 3_multi_object_goal_selector.cpp:172-215 cloudCallback's front half, batched over n_clouds clouds: points are
+ * device float32 rows of point_stride floats (x, y first; 2 or 3), cloud j = rows [offsets_host[j],
+ * offsets_host[j+1]) in message order, at most OT_SCAN_CLUSTER_MAX_BEAMS rows each.  Consecutive points further
+ * apart than cluster_distance_threshold split clusters (:181-189, no seam merge); clusters below
+ * min_cluster_points are dropped; clusters whose bounding box is thinner than wall_thickness_threshold are
+ * skipped (:200).  Each remaining cluster gives one row (cx, cy, width, height, lock_radius) as float: the box
+ * midpoint through poses_host[j] (global <- cloud frame, NULL = identity), lock_radius = diagonal / 2 +
+ * lock_margin (:134-137).  Rows of cloud j start at out_rows + 5 * offsets_host[j] (capacity: 5 floats per input
+ * point); n_obs_host int32 [n_clouds] receives their counts. */
+ot_status ot_cluster_observations(const float* points, int32_t point_stride, const int64_t* offsets_host,
+                                  int32_t n_clouds, const double* poses_host, const ot_observation_params* params,
+                                  float* out_rows, int32_t* n_obs_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

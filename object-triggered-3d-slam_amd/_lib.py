@@ -121,6 +121,10 @@ SIGNATURES = {
     "ot_change_grid_destroy": [_p],
     "ot_change_grid_update": [_p, _p, _p, _i64, _d],
     "ot_change_grid_publish": [_p, _p, _i64, _pi64],
+    "ot_scan_cluster": [_p, _i32, _i32, C.c_float, C.c_float, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                        _p],
+    "ot_object_map_filter": [_p, _p, _i32, _p, _i32, C.c_float, C.c_float, C.c_float, _p, _d, _p, _p, _p, _p],
+    "ot_cluster_observations": [_p, _i32, _p, _i32, _p, _p, _p, _p, _p],
     "ot_rgbd_filter_create": [_pint, _i32, _d, _d, _d, _i32, _d, C.POINTER(_p)],
     "ot_rgbd_filter_destroy": [_p],
     "ot_rgbd_filter_run": [_p, _i32, _p, _p, _p, _p],

@@ -13,6 +13,11 @@ Host-side mirrors of the reference's change-detection code, backed by the HIP ke
   (VirtualScanNode): the scan the saved map would return at each robot pose (the diff node's /virtual_scan input),
   ray-marched per beam on the GPU; ``occupancy_from_pgm`` / ``tf2_get_yaw`` prepare its inputs.
 
+* ``LidarClusterer`` / ``ObjectMapFilter`` / ``cluster_observations`` — the object trigger between the scans and
+  the ScanObject goal: lidar_cluster_publisher.cpp (gap clusters of a scan, WALL / OBJECT / UNKNOWN),
+  object_filter.cpp (object points near a wall of the virtual scan are dropped) and the clustering front half of
+  3_multi_object_goal_selector.cpp (one observation per remaining cluster), each batched over scans.
+
 Every compute call goes through the C ABI; there is no CPU implementation in this module.
 """
 from __future__ import annotations
@@ -241,3 +246,148 @@ def _as_dev(a, dtype):
     if D.is_tensor(a):
         return a.contiguous()
     return D.to_device(np.ascontiguousarray(np.asarray(a, dtype=dtype)))
+
+
+# ------------------------------------------------------------------------------------------------ object trigger
+SCAN_CLASS_NONE, SCAN_CLASS_WALL, SCAN_CLASS_OBJECT, SCAN_CLASS_UNKNOWN = 0, 1, 2, 3
+CLUSTER_ROW = np.dtype([("first_beam", "<i4"), ("n_points", "<i4"), ("length", "<f4"), ("cls", "<i4"),
+                        ("linearity", "<f8")])  # ot_scan_cluster_row
+
+
+class _ClusterParams(C.Structure):  # ot_scan_cluster_params
+    _fields_ = [("gap_threshold", C.c_float), ("min_cluster_points", C.c_int32), ("max_range_ratio", C.c_float),
+                ("obj_len_max", C.c_float), ("wal_len_min", C.c_float), ("wal_lin_max", C.c_float),
+                ("obj_nmp_min", C.c_int32), ("wal_nmp_min", C.c_int32)]
+
+
+class _ObservationParams(C.Structure):  # ot_observation_params
+    _fields_ = [("cluster_distance_threshold", C.c_double), ("wall_thickness_threshold", C.c_double),
+                ("lock_margin", C.c_double), ("min_cluster_points", C.c_int32)]
+
+
+def _poses7(poses, n):
+    if poses is None:
+        return None, None
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(n, 7))
+    return P, P.ctypes.data_as(C.c_void_p)
+
+
+@dataclass
+class ScanClusters:
+    """LidarClusterer.process's result for S scans of N beams.  Per beam (numpy): ``beam_cluster`` int32 [S][N] (index
+    in the scan's cluster list, -1 = none), ``beam_class`` uint8 [S][N] (SCAN_CLASS_*), ``beam_xy`` float32 [S][N][2]
+    (map frame; NaN for invalid beams).  ``clusters[s]``: the scan's cluster table (CLUSTER_ROW records).  The
+    three published clouds stay on the device, concatenated over scans (``wall_xyz`` / ``object_xyz`` /
+    ``unknown_xyz`` float32 [k][3]) with host row offsets int64 [S + 1] (``wall_offsets`` ...); ``wall_cloud(s)``,
+    ``object_cloud(s)``, ``unknown_cloud(s)`` return one scan's cloud as numpy."""
+
+    beam_cluster: np.ndarray
+    beam_class: np.ndarray
+    beam_xy: np.ndarray
+    n_clusters: np.ndarray
+    clusters: list
+    wall_xyz: object
+    object_xyz: object
+    unknown_xyz: object
+    wall_offsets: np.ndarray
+    object_offsets: np.ndarray
+    unknown_offsets: np.ndarray
+
+    def wall_cloud(self, s):
+        return D.to_host(self.wall_xyz[self.wall_offsets[s]:self.wall_offsets[s + 1]])
+
+    def object_cloud(self, s):
+        return D.to_host(self.object_xyz[self.object_offsets[s]:self.object_offsets[s + 1]])
+
+    def unknown_cloud(self, s):
+        return D.to_host(self.unknown_xyz[self.unknown_offsets[s]:self.unknown_offsets[s + 1]])
+
+
+class LidarClusterer:
+    """LidarClusterPublisher (lidar_cluster_publisher.cpp): the node's parameters with its defaults and its scan
+    callback, batched over scans on the GPU (ot_scan_cluster).  Linearity is the float64 definition of DESIGN.md §4;
+    a single cluster closing on itself across the seam is kept once."""
+
+    def __init__(self, gap_threshold=0.2, min_cluster_points=1, max_range_ratio=1.0, obj_len_max=1.0,
+                 wal_len_min=2.0, wal_lin_max=0.001, obj_nmp_min=1, wal_nmp_min=20):
+        self._params = _ClusterParams(float(gap_threshold), int(min_cluster_points), float(max_range_ratio),
+                                      float(obj_len_max), float(wal_len_min), float(wal_lin_max), int(obj_nmp_min),
+                                      int(wal_nmp_min))
+
+    def process(self, ranges, meta: LaserScan, poses=None) -> ScanClusters:
+        """ranges float32 [S][N] (numpy or device tensor), meta: the scans' angle_min / angle_increment / range_max,
+        poses [S][7] = (tx, ty, tz, qx, qy, qz, qw) map <- base_link (None = identity)."""
+        R = _as_dev(ranges, np.float32)
+        if R.dim() != 2:
+            raise RuntimeError("[LidarClusterer] ranges must be [n_scans][n_beams]")
+        S, N = int(R.shape[0]), int(R.shape[1])
+        P, pp = _poses7(poses, S)
+        bc, bk = D.empty((S, N), "int32"), D.empty((S, N), "uint8")
+        bxy = D.empty((S, N, 2), "float32")
+        nc = D.empty((S,), "int32")
+        rows = D.empty((S, N * CLUSTER_ROW.itemsize), "uint8")
+        clouds = [D.empty((max(S * N, 1), 3), "float32") for _ in range(3)]
+        off = np.zeros((3, S + 1), np.int64)
+        L.call("ot_scan_cluster", D.ptr(R), S, N, float(meta.angle_min), float(meta.angle_increment),
+               float(meta.range_max), pp, C.byref(self._params), D.ptr(bc), D.ptr(bk), D.ptr(bxy), D.ptr(nc),
+               D.ptr(rows), D.ptr(clouds[0]), D.ptr(clouds[1]), D.ptr(clouds[2]), off.ctypes.data_as(C.c_void_p),
+               D.stream_ptr())
+        n_clusters = D.to_host(nc)
+        table = D.to_host(rows).view(CLUSTER_ROW).reshape(S, N) if S else np.zeros((0, N), CLUSTER_ROW)
+        return ScanClusters(D.to_host(bc), D.to_host(bk), D.to_host(bxy), n_clusters,
+                            [table[s, :n_clusters[s]].copy() for s in range(S)],
+                            clouds[0][:off[0, S]], clouds[1][:off[1, S]], clouds[2][:off[2, S]], off[0], off[1], off[2])
+
+
+class ObjectMapFilter:
+    """ObjectMapFilter (object_filter.cpp), batched over scans (ot_object_map_filter): object points within
+    proximity_threshold of a wall point of the scan's virtual scan are dropped."""
+
+    def __init__(self, proximity_threshold=0.5):
+        self.proximity_threshold = float(proximity_threshold)
+
+    def process(self, object_xyz, offsets, virtual_ranges, virtual_meta: LaserScan, poses=None):
+        """object_xyz float32 [n][3] concatenated over scans (numpy or device tensor) with row offsets [S + 1];
+        virtual_ranges float32 [S][N]; poses [S][7] map <- scan frame (None = identity).  Returns (kept points as a
+        device tensor [k][3], their offsets int64 [S + 1], keep mask uint8 [n] numpy)."""
+        V = _as_dev(virtual_ranges, np.float32)
+        if V.dim() != 2:
+            raise RuntimeError("[ObjectMapFilter] virtual_ranges must be [n_scans][n_beams]")
+        S, N = int(V.shape[0]), int(V.shape[1])
+        off = np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(S + 1))
+        O = _as_dev(object_xyz, np.float32).reshape(-1, 3)
+        n = int(O.shape[0])
+        if n != int(off[-1]):
+            raise RuntimeError("[ObjectMapFilter] offsets do not cover object_xyz")
+        P, pp = _poses7(poses, S)
+        mask = D.empty((max(n, 1),), "uint8")
+        out = D.empty((max(n, 1), 3), "float32")
+        out_off = np.zeros(S + 1, np.int64)
+        L.call("ot_object_map_filter", D.ptr(O) if n else None, off.ctypes.data_as(C.c_void_p), S, D.ptr(V), N,
+               float(virtual_meta.angle_min), float(virtual_meta.angle_increment), float(virtual_meta.range_max), pp,
+               self.proximity_threshold, D.ptr(mask), D.ptr(out), out_off.ctypes.data_as(C.c_void_p), D.stream_ptr())
+        return out[:out_off[S]], out_off, D.to_host(mask[:n])
+
+
+def cluster_observations(points, offsets, poses=None, cluster_distance_threshold=0.4, min_cluster_points=10,
+                         wall_thickness_threshold=0.2, lock_margin=0.5):
+    """3_multi_object_goal_selector.cpp:172-215 (ot_cluster_observations): float32 points [n][2 or 3] (numpy or device
+    tensor) of several clouds in message order with row offsets [n_clouds + 1]; poses [n_clouds][7] global <- cloud
+    frame (None = identity).  Returns one float32 [k][5] array per cloud: (cx, cy, width, height, lock_radius) of its
+    clusters, in cluster order.  The candidate / stable tracker that consumes them is host state outside this
+    package."""
+    X = _as_dev(points, np.float32)
+    if X.dim() != 2 or int(X.shape[1]) not in (2, 3):
+        raise RuntimeError("[cluster_observations] points must be [n][2] or [n][3]")
+    off = np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(-1))
+    J, n = off.size - 1, int(X.shape[0])
+    if J < 0 or n != int(off[-1]):
+        raise RuntimeError("[cluster_observations] offsets do not cover points")
+    P, pp = _poses7(poses, J)
+    prm = _ObservationParams(float(cluster_distance_threshold), float(wall_thickness_threshold), float(lock_margin),
+                             int(min_cluster_points))
+    rows = D.empty((max(n, 1), 5), "float32")
+    n_obs = np.zeros(max(J, 1), np.int32)
+    L.call("ot_cluster_observations", D.ptr(X) if n else None, int(X.shape[1]), off.ctypes.data_as(C.c_void_p), J, pp,
+           C.byref(prm), D.ptr(rows), n_obs.ctypes.data_as(C.c_void_p), D.stream_ptr())
+    return [D.to_host(rows[off[j]:off[j] + n_obs[j]]) for j in range(J)]
