@@ -353,6 +353,24 @@ ot_status ot_tsdf_mesh_vertex_normals(ot_tsdf* vol, int64_t serial, const double
  * int32 [T][3] = the unit key of its cube. */
 ot_status ot_tsdf_fetch_mesh_keys(ot_tsdf* vol, int32_t* vertex_keys, int32_t* triangle_units, void* stream);
 
+/* volume.extract_point_cloud() -- ScalableTSDFVolume::ExtractPointCloud: one point per grid edge
+ * whose two usable voxels (weight != 0, tsdf in [-0.98, 0.98)) have tsdf of opposite sign, with the interpolated colour
+ * and the normal of GetNormalAt (central differences of the trilinear tsdf).  Two phases like the mesh's: _count
+ * integrates the queued frames, counts and returns the number of points (one read-back); _emit then writes points
+ * f64 [n][3], normals f64 [n][3] and colours f64 [n][3] (0..1; NULL to skip; a NoColor volume has none and leaves the
+ * array untouched) into device arrays of that size, in stream order.  Canonical order (Open3D's is hash order): unit
+ * key, voxel x*256 + y*16 + z, axis.  _emit fails with OT_ERR_INVALID_ARGUMENT once the volume has changed since the
+ * count.  The volume and its extracted mesh are left as they are.  A spatially sharded volume (ot_tsdf_set_shard,
+ * ot_tsdf_set_shard_sector) is refused with OT_ERR_INVALID_ARGUMENT: the normals read units of other shards; extract
+ * from the volume distributed.assemble_sharded_volume builds instead. */
+ot_status ot_tsdf_extract_point_cloud_count(ot_tsdf* vol, int64_t* n_points_host, void* stream);
+ot_status ot_tsdf_emit_point_cloud(ot_tsdf* vol, double* points, double* normals, double* colors, void* stream);
+/* volume.extract_voxel_point_cloud() -- ScalableTSDFVolume::ExtractVoxelPointCloud: the centre
+ * of every usable voxel, coloured (c, c, c) with c = (tsdf + 1) / 2; no normals.  The same two phases, order, refusal
+ * of sharded volumes and validity as above (either count serves both emissions); points and colours f64 [n][3]. */
+ot_status ot_tsdf_extract_voxel_point_cloud_count(ot_tsdf* vol, int64_t* n_points_host, void* stream);
+ot_status ot_tsdf_emit_voxel_point_cloud(ot_tsdf* vol, double* points, double* colors, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Triangle meshes
  * ------------------------------------------------------------------------------------------------- */

@@ -191,6 +191,17 @@ struct MeshBuffers {
     int64_t cap_v = 0, cap_t = 0, cap_vk = 0, cap_tk = 0, cap_vown = 0;
 };
 
+// Per-unit counts and output bases of the last point-cloud count (tsdf_cloud.hip), by unit rank in key order: the
+// zero-crossing cloud's points and the voxel cloud's points.  Its own workspace: a cloud extraction leaves the
+// marching-cubes structure (MeshBuffers) as it is.
+struct CloudBuffers {
+    void* ws = nullptr;  // long long [4][units]: surface counts, voxel counts, surface bases, voxel bases
+    size_t ws_bytes = 0;
+    int64_t units = 0;
+    int64_t n_surface = 0, n_voxel = 0;
+    bool valid = false;  // cleared by anything that changes the volume (integrate, reset, import)
+};
+
 }  // namespace ot
 
 struct ot_tsdf {
@@ -265,6 +276,7 @@ struct ot_tsdf {
     int sorted_frame = -1;
     // extracted mesh
     ot::MeshBuffers mesh;
+    ot::CloudBuffers cloud;
     // a second stream for independent extraction stages (vertex positions beside triangle indices), fork / join
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;

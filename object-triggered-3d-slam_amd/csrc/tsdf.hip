@@ -2344,7 +2344,8 @@ ot_status tsdf_flush(ot_tsdf* vol, hipStream_t stream, bool join) {
     size_t i = 0;
     std::vector<PendingFrame> frames;
     frames.swap(vol->pending);
-    if (!frames.empty()) vol->mesh.valid = false;  // the volume changes: the last extraction's structure is stale
+    // the volume changes: the last extractions' structures are stale
+    if (!frames.empty()) vol->mesh.valid = vol->cloud.valid = false;
     while (i < frames.size()) {
         // a batch: consecutive frames with identical intrinsics, at most batch_max (<= 64)
         size_t n = 1;
@@ -2585,7 +2586,7 @@ ot_status ot_tsdf_destroy(ot_tsdf* v) {
     ot_tsdf_set_profiling(v, 0);
     void* ptrs[] = {d.hkeys, d.hvals, d.counters, d.stats, d.unit_keys, d.vox, v->mult, v->sorted_ids, v->mesh.ws,
                     v->mesh.v, v->mesh.c, v->mesh.t, v->mesh.vk, v->mesh.tk, v->mesh.vown, d.fmask, d.bslots, d.work,
-                    v->wcount, v->bset[0].bframes, v->bset[0].bdc, v->bset[1].bframes, v->bset[1].bdc,
+                    v->cloud.ws, v->wcount, v->bset[0].bframes, v->bset[0].bdc, v->bset[1].bframes, v->bset[1].bdc,
                     v->bset[1].work, v->tmask};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -2629,6 +2630,7 @@ ot_status ot_tsdf_reset(ot_tsdf* v) {
     v->sorted_units = -1;
     v->mesh.nv = v->mesh.nt = 0;
     v->mesh.valid = false;
+    v->cloud.valid = false;
     return OT_OK;
 }
 
@@ -2654,6 +2656,7 @@ ot_status ot_tsdf_reset_async(ot_tsdf* v, void* stream_) {
     v->sorted_units = -1;
     v->mesh.nv = v->mesh.nt = 0;
     v->mesh.valid = false;
+    v->cloud.valid = false;
     return OT_OK;
 }
 
@@ -3038,6 +3041,7 @@ static ot_status import_units(ot_tsdf* vol, int64_t n, const int32_t* keys, cons
     vol->imported = true;    // arbitrary state: the IEEE-division integrate from now on
     vol->stat_prev_units = -1;
     vol->mesh.valid = false;
+    vol->cloud.valid = false;
     st = check_errors(vol, stream);
     if (st != OT_OK) return st;
     OT_HIP_TRY(hipStreamSynchronize(stream));
@@ -3105,6 +3109,7 @@ ot_status ot_tsdf_import_border(ot_tsdf* vol, int64_t n, const int32_t* keys, co
     vol->imported = true;  // halo units hold other shards' state (read by marching cubes; kept exact anyway)
     vol->stat_prev_units = -1;
     vol->mesh.valid = false;
+    vol->cloud.valid = false;
     st = check_errors(vol, stream);
     if (st != OT_OK) return st;
     OT_HIP_TRY(hipStreamSynchronize(stream));

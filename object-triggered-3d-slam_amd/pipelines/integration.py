@@ -305,6 +305,40 @@ class ScalableTSDFVolume:
             return mesh, None
         return mesh, mesh.sample_points_min_z(number_of_points, z_min, seed)
 
+    def extract_point_cloud(self):
+        """ScalableTSDFVolume::ExtractPointCloud — the zero-crossing cloud with normals and (RGB8 volumes) colours
+        (tsdf_cloud.hip).  Points in the canonical order: unit key, voxel, axis.  Not available on a
+        spatially sharded volume (RuntimeError): extract from distributed.assemble_sharded_volume's volume."""
+        n = C.c_int64(0)
+        L.call("ot_tsdf_extract_point_cloud_count", self._h, C.byref(n), D.stream_ptr())
+        self._keep.clear()
+        pcd = PointCloud()
+        if n.value == 0:
+            return pcd
+        P = D.empty((n.value, 3), "float64")
+        N = D.empty((n.value, 3), "float64")
+        PC = D.empty((n.value, 3), "float64") if self.color_type == TSDFVolumeColorType.RGB8 else None
+        L.call("ot_tsdf_emit_point_cloud", self._h, D.ptr(P), D.ptr(N), D.ptr(PC), D.stream_ptr())
+        pcd._xyz, pcd._nrm = _Arr(dev=P), _Arr(dev=N)
+        pcd._rgb = _Arr(dev=PC) if PC is not None else None
+        return pcd
+
+    def extract_voxel_point_cloud(self):
+        """ScalableTSDFVolume::ExtractVoxelPointCloud — the centres of the observed voxels (weight != 0, tsdf in
+        [-0.98, 0.98)), coloured (c, c, c) with c = (tsdf + 1) / 2; no normals.  Sharded volumes
+        are refused as by extract_point_cloud."""
+        n = C.c_int64(0)
+        L.call("ot_tsdf_extract_voxel_point_cloud_count", self._h, C.byref(n), D.stream_ptr())
+        self._keep.clear()
+        pcd = PointCloud()
+        if n.value == 0:
+            return pcd
+        P = D.empty((n.value, 3), "float64")
+        PC = D.empty((n.value, 3), "float64")
+        L.call("ot_tsdf_emit_voxel_point_cloud", self._h, D.ptr(P), D.ptr(PC), D.stream_ptr())
+        pcd._xyz, pcd._rgb = _Arr(dev=P), _Arr(dev=PC)
+        return pcd
+
     def extract_triangle_mesh(self, with_keys=False):
         """ScalableTSDFVolume::ExtractTriangleMesh — GPU marching cubes (mc.hip).  with_keys: also return the merge
         keys (vertex (U,4) int32 = owner unit key + edge bit, triangle (T,3) int32 = its cube's unit key) that
