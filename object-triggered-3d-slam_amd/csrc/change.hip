@@ -180,7 +180,9 @@ __global__ __launch_bounds__(256) void k_lattice_keys_obj(const double* __restri
     unsigned long long f[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) f[a] = (unsigned long long)((int)floor((xyz[i * 3 + a] - o[a]) / vs) - lay.mn[a]);
-    keys[i] = ((unsigned long long)obj << lay.so) | (f[0] << lay.sx) | (f[1] << lay.sy) | f[2];
+    // so == 64: the cell fields fill the key and the only object is 0 (a shift by 64 is undefined)
+    const unsigned long long ob = lay.so < 64 ? (unsigned long long)obj << lay.so : 0ull;
+    keys[i] = ob | (f[0] << lay.sx) | (f[1] << lay.sy) | f[2];
 }
 
 struct ObjKeyEmit {
@@ -189,7 +191,7 @@ struct ObjKeyEmit {
     ObjLayout lay;
     __device__ void operator()(int64_t i, int64_t pos) const {
         const unsigned long long k = a[i];
-        out[pos * 4 + 0] = (int)(k >> lay.so);
+        out[pos * 4 + 0] = lay.so < 64 ? (int)(k >> lay.so) : 0;
         out[pos * 4 + 1] = (int)((k >> lay.sx) & ((1ull << (lay.so - lay.sx)) - 1ull)) + lay.mn[0];
         out[pos * 4 + 2] = (int)((k >> lay.sy) & ((1ull << (lay.sx - lay.sy)) - 1ull)) + lay.mn[1];
         out[pos * 4 + 3] = (int)(k & ((1ull << lay.sy) - 1ull)) + lay.mn[2];

@@ -25,6 +25,14 @@ inline double sor_cell_target(int nb_neighbors) {
     return t > 2.0 ? t : 2.0;
 }
 
+// ROR (outlier.hip): cells are this factor wider than the radius.  A point's cell is floor((v - origin) / h) with the
+// subtraction and the division each rounded, so the computed cell quotients of two points d apart differ from d / h by
+// up to 2^-31 (each quotient is below 2^20 cells and carries two roundings of 2^-53 relative).  With h = radius
+// exactly, a pair a hair under the radius apart can land in cells that differ by 2 and the 3x3x3 block never meets
+// it (tests/test_gpu_ror_edges.py builds such pairs); with d / h <= 1 - 2^-21 it cannot.  Only the candidate set
+// grows: counts and kept indices are unchanged wherever no neighbour was missed.
+constexpr double ROR_CELL_SCALE = 1.0 + 1.0 / (double)(1 << 20);
+
 // neighbour structures a grid build can precompute (bit mask)
 enum { GRID_NBR3 = 1, GRID_NBR5 = 2 };
 constexpr int SOR_GRID_NBR = GRID_NBR3;

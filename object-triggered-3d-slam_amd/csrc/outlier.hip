@@ -6,7 +6,8 @@
 //   grid build : (frame, cell) key per point -> stable radix sort -> cell heads -> open-addressing hash (cell key ->
 //                [start, end) in the sorted order) -> per cell the z-column ranges of its 3x3 / 5x5 block; points
 //                are re-laid out in sorted order so a cell's points are contiguous in HBM.
-//   ROR        : cell = radius; count |{j : d2(i, j) < r^2}| over the 27 neighbour cells (exact integers).
+//   ROR        : cell = radius * ROR_CELL_SCALE (grid.h: a rounding margin, so no neighbour falls outside the
+//                block); count |{j : d2(i, j) < r^2}| over the 27 neighbour cells (exact integers).
 //   SOR        : exact k nearest neighbours: the columns of the query's block are scanned nearest-first into a
 //                register-resident sorted top-k list (columns that cannot hold a closer point are skipped) until the
 //                k-th distance is provably inside the scanned block, else Chebyshev rings continue it.  Distances
@@ -139,7 +140,8 @@ __global__ __launch_bounds__(256) void k_gather_sorted(const double* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ ROR
-// cell = radius: every neighbour within the radius lies in the 3x3x3 block, i.e. in the 9 merged ranges.
+// cell = radius * ROR_CELL_SCALE: every neighbour within the radius lies in the 3x3x3 block of the query's COMPUTED
+// cell (grid.h has the rounding argument), i.e. in the 9 merged ranges.
 __global__ __launch_bounds__(256) void k_ror(GridDev g, int64_t n, double r2, int nb, unsigned char* keep) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
@@ -1101,7 +1103,7 @@ ot_status ot_remove_radius_outlier(const double* xyz, int64_t n, int32_t nb_poin
     ot_status st = bounds_host(xyz, n, stream, mn, mx);
     if (st != OT_OK) return st;
     GridBuild gb;
-    st = single_frame_grid(xyz, n, radius, mn, mx, GRID_NBR3, stream, gb);
+    st = single_frame_grid(xyz, n, radius * ROR_CELL_SCALE, mn, mx, GRID_NBR3, stream, gb);
     if (st != OT_OK) return st;
     unsigned char* keep = (unsigned char*)scratch((size_t)n + 64, 12);
     if (!keep) return fail(OT_ERR_HIP, "scratch allocation failed");

@@ -748,7 +748,11 @@ int64_t oro_remove_radius_outlier(const double* xyz, int64_t n, int nb_points, d
     if (nb_points < 1 || radius <= 0) return -1;
     if (n == 0) return 0;
     Grid g;
-    build_grid(g, xyz, n, radius);
+    // Open3D's radius search returns EVERY point with dist2 < r2; the grid only finds them.  key_of rounds (p - mn)
+    // and the division separately (up to 2^-31 on the difference of two cell quotients below 2^20), so cells of
+    // exactly the radius can put a pair a hair under the radius apart two cells apart, outside the 3x3x3 block
+    // (tests/ror_ref.py constructs such pairs).  Cells wider by 2^-20 cannot.
+    build_grid(g, xyz, n, radius * (1.0 + 1.0 / (double)(1 << 20)));
     const double r2 = radius * radius;
     std::vector<char> mask(n, 0);
 #pragma omp parallel for schedule(static)
