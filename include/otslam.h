@@ -97,6 +97,18 @@ ot_status ot_remove_statistical_outlier(const double* xyz, int64_t n, int32_t nb
 ot_status ot_remove_radius_outlier(const double* xyz, int64_t n, int32_t nb_points, double radius,
                                    int64_t* out_indices, int64_t* n_kept_host, void* stream);
 
+/* geometry.PointCloud.cluster_dbscan(eps, min_points) — Open3D's PointCloud::ClusterDBSCAN ("DBSCAN").
+ * With d2(i, j) = ((dx dx) + dy dy) + dz dz in float64 (ROR's test): point i is a core point when
+ * |{j : d2(i, j) < eps^2}| >= min_points (i itself counts, so min_points 0 and 1 make every point core); clusters are
+ * the connected components of the core points under d2 < eps^2, numbered 0 .. C-1 by ascending smallest point index
+ * among their core members; a non-core point takes the smallest label among the core points within eps of it, and
+ * -1 (noise) when there is none.  These are the labels of Open3D's index-order loop.  out_labels: device int32 [n] in
+ * input order; *n_clusters_host (nullable) receives C.  eps must be finite and > 0 and min_points >= 0
+ * (OT_ERR_INVALID_ARGUMENT, checked before any device work); n == 0 returns at once. */
+ot_status ot_cluster_dbscan(const double* xyz, int64_t n, double eps, int32_t min_points,
+                            int32_t* out_labels /* device [n], input order */,
+                            int32_t* n_clusters_host, void* stream);
+
 /* Stable compaction `mask = points[:, 2] >= z_min` — reconstruct_rgbd_filter.py:126-132.
  * rgb may be NULL.  Output buffers hold n rows. */
 ot_status ot_filter_min_z(const double* xyz, const double* rgb, int64_t n, double z_min,

@@ -9,13 +9,14 @@ from __future__ import annotations
 
 import ctypes as C
 import importlib
+import math
 
 import numpy as np
 
 from . import _device as D
 from . import _lib as L
 from . import streams as _streams
-from .utility import DoubleVector, Vector3dVector, Vector3iVector
+from .utility import DoubleVector, IntVector, Vector3dVector, Vector3iVector
 
 
 class _Arr:
@@ -448,6 +449,21 @@ class PointCloud:
                C.byref(k), D.stream_ptr())
         idx = idx[:k.value]
         return self._select_dev(idx), D.to_host(idx).tolist()
+
+    def cluster_dbscan(self, eps, min_points, print_progress=False):
+        """PointCloud::ClusterDBSCAN — ot_cluster_dbscan.  One label per point (Python ints): 0 .. C-1 for the
+        clusters, -1 for noise."""
+        if not (eps > 0 and math.isfinite(eps)) or min_points < 0:
+            raise RuntimeError("[ClusterDBSCAN] Illegal input parameters, eps must be positive and finite and "
+                               "min_points must not be negative")
+        n = len(self._xyz)
+        if n == 0:
+            return IntVector()
+        labels = D.empty((n,), "int32")
+        k = C.c_int32(0)
+        L.call("ot_cluster_dbscan", D.ptr(self._xyz.dev()), n, float(eps), int(min_points), D.ptr(labels),
+               C.byref(k), D.stream_ptr())
+        return IntVector(D.to_host(labels).tolist())
 
     def compute_point_cloud_distance(self, target):
         """PointCloud::ComputePointCloudDistance (eval_cone.py:99,103) — ot_compute_point_cloud_distance.
