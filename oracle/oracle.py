@@ -49,6 +49,7 @@ def lib():
             "oro_tsdf_total_updates": (_i64, [_p]),
             "oro_tsdf_unit_integrations": (_i64, [_p]),
             "oro_tsdf_export": (None, [_p, _p, _p, _p, _p]),
+            "oro_tsdf_import": (None, [_p, _i64, _p, _p, _p, _p]),
             "oro_tsdf_extract_mesh": (None, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
             "oro_tsdf_fetch_mesh": (None, [_p, _p, _p, _p]),
             "oro_mesh_vertex_normals": (None, [_p, _i64, _p, _i64, _p]),
@@ -164,6 +165,18 @@ class TSDF:
         color = np.empty((u, 4096, 3), np.float64)
         lib().oro_tsdf_export(self.h, _ptr(keys), _ptr(tsdf), _ptr(weight), _ptr(color))
         return keys, tsdf, weight, color
+
+    def import_units(self, keys, tsdf, weight, color=None):
+        """Insert units in export()'s layouts (the inverse of export; a unit with the same key is overwritten,
+        color=None means zeros): how a test gives the oracle a designed volume."""
+        keys = _c(keys, np.int32).reshape(-1, 3)
+        n = keys.shape[0]
+        tsdf = _c(tsdf, np.float32)
+        weight = _c(weight, np.float32)
+        color = _c(color, np.float64)
+        if tsdf.shape != (n, 4096) or weight.shape != (n, 4096) or (color is not None and color.shape != (n, 4096, 3)):
+            raise ValueError("import_units: shapes do not match export()")
+        lib().oro_tsdf_import(self.h, n, _ptr(keys), _ptr(tsdf), _ptr(weight), _ptr(color))
 
     def extract_triangle_mesh(self):
         nv, nt = C.c_int64(0), C.c_int64(0)

@@ -395,6 +395,22 @@ void oro_tsdf_export(void* h, int32_t* keys, float* tsdf, float* weight, double*
     }
 }
 
+/* The inverse of oro_tsdf_export (ot_tsdf_import_units' semantics): insert n units in export's layouts, overwriting a
+ * unit with the same key; color == NULL means zeros.  Lets a test hand the oracle a designed volume. */
+void oro_tsdf_import(void* h, int64_t n, const int32_t* keys, const float* tsdf, const float* weight,
+                     const double* color) {
+    Tsdf& vol = *(Tsdf*)h;
+    for (int64_t i = 0; i < n; ++i) {
+        Unit& u = vol.units[Key3{keys[i * 3 + 0], keys[i * 3 + 1], keys[i * 3 + 2]}];
+        std::memcpy(u.tsdf.data(), tsdf + i * NVOX, sizeof(float) * NVOX);
+        std::memcpy(u.weight.data(), weight + i * NVOX, sizeof(float) * NVOX);
+        if (color)
+            std::memcpy(u.color.data(), color + i * NVOX * 3, sizeof(double) * NVOX * 3);
+        else
+            std::fill(u.color.begin(), u.color.end(), 0.0);
+    }
+}
+
 /* ScalableTSDFVolume::ExtractTriangleMesh (Appendix A.4), units visited in sorted key order.  Vertices are
  * then renumbered canonically: sorted by (owner unit key, local voxel IndexOf, axis) of their edge key. */
 void oro_tsdf_extract_mesh(void* h, int64_t* nv, int64_t* nt) {

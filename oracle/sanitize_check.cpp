@@ -25,6 +25,8 @@ int64_t oro_tsdf_num_units(void* h);
 int64_t oro_tsdf_total_updates(void* h);
 int64_t oro_tsdf_unit_integrations(void* h);
 void oro_tsdf_export(void* h, int32_t* keys, float* tsdf, float* weight, double* color);
+void oro_tsdf_import(void* h, int64_t n, const int32_t* keys, const float* tsdf, const float* weight,
+                     const double* color);
 void oro_tsdf_extract_mesh(void* h, int64_t* nv, int64_t* nt);
 void oro_tsdf_fetch_mesh(void* h, double* V, double* VC, int32_t* T);
 void oro_mesh_vertex_normals(const double* V, int64_t nv, const int32_t* T, int64_t nt, double* N);
@@ -122,6 +124,20 @@ int main() {
         std::vector<float> t(units * 4096), w(units * 4096);
         std::vector<double> c(units * 4096 * 3);
         oro_tsdf_export(vol, k.data(), t.data(), w.data(), c.data());
+        // import: the exported units into a fresh volume give the same mesh sizes; a second import of the first unit
+        // without colours overwrites it in place
+        void* copy = oro_tsdf_create(0.01, 0.04, 1, 1);
+        oro_tsdf_import(copy, units, k.data(), t.data(), w.data(), c.data());
+        CHECK(oro_tsdf_num_units(copy) == units);
+        int64_t cv = 0, ct = 0, ov = 0, ot = 0;
+        oro_tsdf_extract_mesh(copy, &cv, &ct);
+        oro_tsdf_extract_mesh(vol, &ov, &ot);
+        CHECK(cv == ov && ct == ot);
+        oro_tsdf_import(copy, 1, k.data(), t.data(), w.data(), nullptr);
+        CHECK(oro_tsdf_num_units(copy) == units);
+        oro_tsdf_extract_mesh(copy, &cv, &ct);
+        CHECK(cv == ov && ct == ot);
+        oro_tsdf_destroy(copy);
     }
     int64_t mv = 0, mt = 0;
     oro_tsdf_extract_mesh(vol, &mv, &mt);

@@ -145,6 +145,106 @@ def test_mesh_of_wall_lies_on_wall(O):
     assert T.min() >= 0 and T.max() < V.shape[0]
 
 
+def _scanned_volume(O):
+    """three frames of a sloping floor with a box on it, from three poses, coloured by pixel"""
+    w, h, fx, fy, cx, cy = 96, 72, 80.0, 80.0, 47.5, 35.5
+    rr, cc = np.mgrid[0:h, 0:w]
+    depth = (1.2 + rr / 400.0).astype(np.float32)
+    depth[20:50, 30:65] = 0.9
+    depth[(rr * 7 + cc * 3) % 97 == 0] = 0.0
+    color = np.stack([cc * 2, rr * 3, (rr * cc) & 255], -1).astype(np.uint8)
+    vol = O.TSDF(0.01, 0.04, 1, 4)
+    for f in range(3):
+        ext = np.eye(4)
+        ext[0, 3] = 0.013 * f
+        ext[2, 3] = -0.004 * f
+        vol.integrate(depth, color, (w, h, fx, fy, cx, cy), ext)
+    return vol
+
+
+def test_tsdf_import_round_trip(O):
+    """import_units followed by export returns the same arrays (units sorted by key whatever the import order); a
+    second import of a key overwrites the unit; no colour means zeros"""
+    rng = np.random.default_rng(21)
+    keys = np.array([[3, -2, 0], [-1, 0, 5], [0, 0, 0], [-1, 0, 4]], np.int32)
+    tsdf = (rng.random((4, 4096), dtype=np.float32) * 2 - 1).astype(np.float32)
+    tsdf[0, :4] = [0.0, -0.0, 1.4e-45, -1.4e-45]
+    weight = rng.integers(0, 5, (4, 4096)).astype(np.float32)
+    color = rng.uniform(0, 255, (4, 4096, 3))
+    vol = O.TSDF(0.01, 0.04, 1, 4)
+    vol.import_units(keys, tsdf, weight, color)
+    order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+    k, t, w, c = vol.export()
+    assert_bitwise(k, keys[order], "round trip keys")
+    assert_bitwise(t, tsdf[order], "round trip tsdf")
+    assert_bitwise(w, weight[order], "round trip weight")
+    assert_bitwise(c, color[order], "round trip colour")
+    vol.import_units(keys[1:2], tsdf[2:3], weight[3:4])  # overwrite (-1, 0, 5), without colours
+    k, t, w, c = vol.export()
+    assert vol.num_units() == 4
+    at = int(np.nonzero(order == 1)[0][0])
+    exp_t, exp_w, exp_c = tsdf[order].copy(), weight[order].copy(), color[order].copy()
+    exp_t[at], exp_w[at], exp_c[at] = tsdf[2], weight[3], 0.0
+    assert_bitwise(k, keys[order], "keys after the overwrite")
+    assert_bitwise(t, exp_t, "tsdf after the overwrite")
+    assert_bitwise(w, exp_w, "weight after the overwrite")
+    assert_bitwise(c, exp_c, "colour after the overwrite")
+
+
+def test_tsdf_import_of_a_scanned_volume_gives_its_mesh(O):
+    vol = _scanned_volume(O)
+    V, VC, T = vol.extract_triangle_mesh()
+    assert V.shape[0] > 1000 and T.shape[0] > 1000
+    copy = O.TSDF(0.01, 0.04, 1, 4)
+    copy.import_units(*vol.export())
+    V2, VC2, T2 = copy.extract_triangle_mesh()
+    assert_bitwise(V2, V, "vertices of the imported volume")
+    assert_bitwise(VC2, VC, "vertex colours of the imported volume")
+    assert_bitwise(T2, T, "triangles of the imported volume")
+
+
+def test_mesh_of_one_cut_corner_kat(O):
+    """One unit, every weight 1 and every tsdf +0.5 except the interior voxel p at -0.25: Open3D's ExtractTriangleMesh
+     cuts the six edges at p, at (0.25 vl / 0.75) from p's centre along +-x, +-y, +-z, and the eight cubes
+    with p as a corner emit one triangle each -- an octahedron.  Written from the formula, by hand:
+
+    vertex on the edge v0 -> v1 (v0 the lower voxel along the axis): centre(v0) + |f0| vl / (|f0| + |f1|), colour
+    (|f1| c0 + |f0| c1) / (|f0| + |f1|) with c = colour / 255.  Canonical vertex order (owner voxel index, axis):
+    0 = -x (owner p - ex), 1 = -y (p - ey), 2 = -z (p - ez), 3 = +x, 4 = +y, 5 = +z (owner p).  Cubes in the order
+    of their origins p - SHIFT[i], i.e. corners i = 6, 2, 5, 1, 7, 3, 4, 0; the table's row for the single corner i
+    (edges a, b, c) is emitted as (a, c, b)."""
+    vl = 0.013
+    key = (-2, 1, 0)
+    p = np.array([5, 6, 7])
+    tsdf = np.full((16, 16, 16), 0.5, np.float32)
+    tsdf[tuple(p)] = -0.25
+    weight = np.ones((16, 16, 16), np.float32)
+    rng = np.random.default_rng(22)
+    color = rng.uniform(0, 255, (16, 16, 16, 3))
+    vol = O.TSDF(vl, 0.04, 1, 4)
+    vol.import_units(np.array([key], np.int32), tsdf.reshape(1, -1), weight.reshape(1, -1), color.reshape(1, -1, 3))
+    V, VC, T = vol.extract_triangle_mesh()
+    half = vl * 0.5
+    expV, expC = [], []
+    for low, f0, f1 in ((True, 0.5, 0.25), (False, 0.25, 0.5)):  # the three edges below p, then the three above
+        for a in range(3):
+            v0 = p.copy()
+            if low:
+                v0[a] -= 1
+            v1 = v0.copy()
+            v1[a] += 1
+            g = np.array(key) * 16 + v0
+            pt = [half + vl * float(g[0]), half + vl * float(g[1]), half + vl * float(g[2])]
+            pt[a] += f0 * vl / (f0 + f1)
+            expV.append(pt)
+            c0, c1 = color[tuple(v0)] / 255.0, color[tuple(v1)] / 255.0
+            expC.append((f1 * c0 + f0 * c1) / (f0 + f1))
+    expT = np.array([(2, 1, 0), (1, 5, 0), (2, 0, 4), (0, 5, 4), (1, 2, 3), (1, 3, 5), (3, 2, 4), (3, 4, 5)], np.int32)
+    assert_bitwise(V, np.array(expV), "octahedron vertices")
+    assert_bitwise(VC, np.array(expC), "octahedron colours")
+    assert_bitwise(T, expT, "octahedron triangles")
+
+
 def _brute_knn_mean(P, k):
     d2 = ((P[:, None, :] - P[None, :, :]) ** 2).sum(-1)
     d2.sort(axis=1)
