@@ -109,6 +109,37 @@ ot_status ot_cluster_dbscan(const double* xyz, int64_t n, double eps, int32_t mi
                             int32_t* out_labels /* device [n], input order */,
                             int32_t* n_clusters_host, void* stream);
 
+/* geometry.PointCloud.estimate_covariances(search_param) — Open3D's EstimatePerPointCovariances (DESIGN.md §4,
+ * "normals").  Neighbours of point i: every point j of the cloud (i included) ordered ascending by (d2, j) with
+ * d2 = ((dx dx) + dy dy) + dz dz in float64; the first min(knn, n) of them, and with radius > 0 (hybrid search) only
+ * those of these with d2 < radius^2 (strict).  radius <= 0: pure KNN.  With m neighbours, m < 3: the identity;
+ * otherwise the nine sums x, y, z, xx, xy, xz, yy, yz, zz over the neighbours in that order (each product rounded,
+ * then added), each divided by (double)m, and C00 = s3 - s0 s0, C01 = s4 - s0 s1, ... (not centred first).
+ * cov_out: device float64 [n][3][3] in input order.  knn must lie in 1..64 and radius must not be NaN
+ * (OT_ERR_INVALID_ARGUMENT, checked before any device work); n == 0 returns at once. */
+ot_status ot_estimate_covariances(const double* xyz, int64_t n, int32_t knn, double radius,
+                                  double* cov_out /* device [n][9] */, void* stream);
+
+/* geometry.PointCloud.estimate_normals(search_param, fast_normal_computation=True): the covariances of
+ * ot_estimate_covariances, then per point the eigenvector of the smallest eigenvalue by Open3D's FastEigen3x3
+ * (the non-iterative symmetric 3x3 solver; DESIGN.md §4 spells out every branch).  A zero result becomes the point's
+ * prior normal, or (0, 0, 1) without priors; with priors the result is negated when its dot product with the prior
+ * is negative.  prior_normals (nullable): device [n][3], may alias normals_out.  cov_out (nullable): receives the
+ * covariances.  Argument rules as ot_estimate_covariances. */
+ot_status ot_estimate_normals(const double* xyz, int64_t n, int32_t knn, double radius, const double* prior_normals,
+                              double* normals_out /* device [n][3] */, double* cov_out /* device [n][9] or NULL */,
+                              void* stream);
+
+/* geometry.PointCloud.orient_normals_to_align_with_direction (mode 0, ref3_host = the direction) and
+ * orient_normals_towards_camera_location (mode 1, ref3_host = the camera location; the reference vector of point i is
+ * then v = ref - xyz[i]), in place.  A zero normal becomes the reference vector (mode 1: v / |v|, or (0, 0, 1) when v
+ * is zero too); any other normal is negated when (nx rx + ny ry) + nz rz < 0.  xyz is read in mode 1 only. */
+ot_status ot_orient_normals(double* normals_inout, const double* xyz, int64_t n, int32_t mode,
+                            const double ref3_host[3], void* stream);
+
+/* geometry.PointCloud.normalize_normals(), in place: n / sqrt((nx nx + ny ny) + nz nz); a zero normal stays zero. */
+ot_status ot_normalize_normals(double* normals_inout, int64_t n, void* stream);
+
 /* Stable compaction `mask = points[:, 2] >= z_min` — reconstruct_rgbd_filter.py:126-132.
  * rgb may be NULL.  Output buffers hold n rows. */
 ot_status ot_filter_min_z(const double* xyz, const double* rgb, int64_t n, double z_min,

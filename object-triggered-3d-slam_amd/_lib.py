@@ -56,6 +56,10 @@ SIGNATURES = {
     "ot_remove_statistical_outlier": [_p, _i64, _i32, _d, _p, _p, _pi64, _p],
     "ot_remove_radius_outlier": [_p, _i64, _i32, _d, _p, _pi64, _p],
     "ot_cluster_dbscan": [_p, _i64, _d, _i32, _p, C.POINTER(C.c_int32), _p],
+    "ot_estimate_covariances": [_p, _i64, _i32, _d, _p, _p],
+    "ot_estimate_normals": [_p, _i64, _i32, _d, _p, _p, _p, _p],
+    "ot_orient_normals": [_p, _p, _i64, _i32, _pd, _p],
+    "ot_normalize_normals": [_p, _i64, _p],
     "ot_compute_point_cloud_distance": [_p, _i64, _p, _i64, _p, _p],
     "ot_transform_points": [_p, _p, _i64, _p, _p, _p, _p],
     "ot_evaluate_registration": [_p, _i64, _p, _i64, _d, _p, _pd, _pd, _p, _pi64, _p],

@@ -127,6 +127,28 @@ __device__ inline double d2_l2(const double* q, const double* p) {
     return ((d0 * d0) + d1 * d1) + d2 * d2;
 }
 
+// the cell the grid assigned to sorted point j (its key): SOR measures every guard from this cell's faces, so a
+// point the rounding of its coordinates puts a hair outside its cell still gets correct (conservative) bounds
+__device__ inline void query_cell(const GridDev& g, int64_t j, int& cx, int& cy, int& cz) {
+    const unsigned long long key = g.pkey[j];
+    cz = (int)(key & ((1ull << g.sy) - 1));
+    cy = (int)((key >> g.sy) & ((1ull << (g.sx - g.sy)) - 1));
+    cx = (int)((key >> g.sx) & ((1ull << (g.sf - g.sx)) - 1));
+}
+
+// distance from q to the faces of the (2R+1)^3 cell block around cell c, minus a rounding margin (f = q's position
+// inside c: in [0, 1) up to rounding; outside it the formula is still q's distance to the block's faces)
+__device__ inline double block_guard(const GridDev& g, const double q[3], const double* o, const int c[3], double R) {
+    double guard = (R + 1.0) * g.h;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double u = (q[a] - o[a]) / g.h;
+        const double f = u - (double)c[a];
+        guard = fmin(guard, fmin(R + f, R + 1.0 - f) * g.h);
+    }
+    return guard - 1e-6 * g.h;
+}
+
 // Build the grid of n points (xyz device [n][3]) grouped in nframes frames.  d_foff / d_origin: device arrays
 // ([F+1] ints, [F][3] doubles) that must outlive the grid; dims: cells per axis covering every frame; nbr: the
 // GRID_* structures to precompute; h_foff (optional host copy of the frame offsets, <= 64 frames): the cell sort

@@ -28,14 +28,6 @@
 
 namespace ot {
 
-// the cell the grid assigned to sorted point j (its key): SOR measures every guard from this cell's faces, so a
-// point the rounding of its coordinates puts a hair outside its cell still gets correct (conservative) bounds
-__device__ inline void query_cell(const GridDev& g, int64_t j, int& cx, int& cy, int& cz) {
-    const unsigned long long key = g.pkey[j];
-    cz = (int)(key & ((1ull << g.sy) - 1));
-    cy = (int)((key >> g.sy) & ((1ull << (g.sx - g.sy)) - 1));
-    cx = (int)((key >> g.sx) & ((1ull << (g.sf - g.sx)) - 1));
-}
 __device__ inline int64_t sor_out(const GridDev& g, int64_t j) { return g.sidx ? (int64_t)g.sidx[j] : j; }
 // the frame of sorted point j: its cell key's frame field (one load, which query_cell makes anyway, instead of a
 // dependent binary search over the frame offsets at the head of every query's chain)
@@ -238,19 +230,6 @@ template <int KMAX>
 __device__ inline void topk_reset(double (&best)[KMAX], int kk) {
 #pragma unroll
     for (int i = 0; i < KMAX; ++i) best[i] = (i < KMAX - kk) ? -INFINITY : INFINITY;
-}
-
-// distance from q to the faces of the (2R+1)^3 cell block around cell c, minus a rounding margin (f = q's position
-// inside c: in [0, 1) up to rounding; outside it the formula is still q's distance to the block's faces)
-__device__ inline double block_guard(const GridDev& g, const double q[3], const double* o, const int c[3], double R) {
-    double guard = (R + 1.0) * g.h;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double u = (q[a] - o[a]) / g.h;
-        const double f = u - (double)c[a];
-        guard = fmin(guard, fmin(R + f, R + 1.0 - f) * g.h);
-    }
-    return guard - 1e-6 * g.h;
 }
 
 // column visiting order of a (2R+1)^2 block, nearest first (t = (dx + R) * (2R + 1) + dy + R)

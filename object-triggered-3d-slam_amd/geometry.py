@@ -213,14 +213,102 @@ class RGBDImage:
         return f"RGBDImage of size\nColor image : {self.color.width}x{self.color.height}\nDepth image : {self.depth.width}x{self.depth.height}"
 
 
+# ------------------------------------------------------------------------------ KDTree search parameters
+class KDTreeSearchParam:
+    """open3d.geometry.KDTreeSearchParam: the base of the three value classes below."""
+
+
+class KDTreeSearchParamKNN(KDTreeSearchParam):
+    def __init__(self, knn=30):
+        self.knn = int(knn)
+
+    def __repr__(self):
+        return f"KDTreeSearchParamKNN with knn = {self.knn}"
+
+
+class KDTreeSearchParamRadius(KDTreeSearchParam):
+    def __init__(self, radius):
+        self.radius = float(radius)
+
+    def __repr__(self):
+        return f"KDTreeSearchParamRadius with radius = {self.radius:f}"
+
+
+class KDTreeSearchParamHybrid(KDTreeSearchParam):
+    def __init__(self, radius, max_nn):
+        self.radius = float(radius)
+        self.max_nn = int(max_nn)
+
+    def __repr__(self):
+        return f"KDTreeSearchParamHybrid with radius = {self.radius:f} and max_nn = {self.max_nn}"
+
+
+def _search_args(who, search_param):
+    """(knn, radius) of the C ABI (radius 0.0: pure KNN), the refusals of DESIGN.md §4 "normals" raised here,
+    before any device work."""
+    if isinstance(search_param, KDTreeSearchParamRadius):
+        raise RuntimeError(f"[{who}] KDTreeSearchParamRadius is not supported: its neighbour list is unbounded and "
+                           "the covariance is a distance-ordered sum over at most 64 neighbours; use "
+                           "KDTreeSearchParamHybrid(radius, max_nn)")
+    if isinstance(search_param, KDTreeSearchParamHybrid):
+        knn, radius, name = search_param.max_nn, search_param.radius, "max_nn"
+        if not radius > 0.0:
+            raise RuntimeError(f"[{who}] KDTreeSearchParamHybrid needs radius > 0, got {radius}")
+    elif isinstance(search_param, KDTreeSearchParamKNN):
+        knn, radius, name = search_param.knn, 0.0, "knn"
+    else:
+        raise RuntimeError(f"[{who}] search_param must be KDTreeSearchParamKNN or KDTreeSearchParamHybrid, got "
+                           f"{type(search_param).__name__}")
+    if not 1 <= knn <= 64:
+        raise RuntimeError(f"[{who}] {name} must lie in 1..64 (the neighbour list is kept on chip), got {knn}")
+    return int(knn), float(radius)
+
+
+class Matrix3dVector:
+    """open3d.utility.Matrix3dVector-like view of an (N, 3, 3) float64 host array (np.asarray returns it uncopied)."""
+
+    def __init__(self, data=None):
+        a = np.zeros((0, 3, 3)) if data is None else np.array(data, dtype=np.float64, copy=True)
+        if a.size == 0:
+            a = a.reshape(0, 3, 3)
+        if a.ndim != 3 or a.shape[1:] != (3, 3):
+            raise RuntimeError(f"Matrix3dVector expects an (N, 3, 3) array, got {a.shape}")
+        self._a = np.ascontiguousarray(a)
+
+    @classmethod
+    def _view(cls, arr):
+        v = cls.__new__(cls)
+        v._a = arr.reshape(-1, 3, 3)
+        return v
+
+    def __array__(self, dtype=None, copy=None):
+        return self._a if dtype is None else self._a.astype(dtype)
+
+    def __len__(self):
+        return self._a.shape[0]
+
+    def __getitem__(self, i):
+        return self._a[i]
+
+    def __setitem__(self, i, v):
+        self._a[i] = v
+
+    def __iter__(self):
+        return iter(self._a)
+
+    def __repr__(self):
+        return f"std::vector<Eigen::Matrix3d> with {len(self)} elements."
+
+
 # ---------------------------------------------------------------------------------------- PointCloud
 class PointCloud:
-    """open3d.geometry.PointCloud with points/colors/normals as float64 (N, 3)."""
+    """open3d.geometry.PointCloud with points/colors/normals as float64 (N, 3) and covariances (N, 3, 3)."""
 
     def __init__(self, points=None):
         self._xyz = _Arr.wrap(points, np.float64, 3) if points is not None else _Arr(host=np.zeros((0, 3)))
         self._rgb = None
         self._nrm = None
+        self._cov = None  # [n][9] rows (the 3x3 matrices row-major)
 
     # --- attribute access (host views) ---
     @property
@@ -249,6 +337,23 @@ class PointCloud:
         a = _Arr.wrap(v, np.float64, 3)
         self._nrm = a if a is not None and len(a) > 0 else None
 
+    @property
+    def covariances(self):
+        h = self._cov.host_view() if self._cov is not None else np.zeros((0, 9))
+        return Matrix3dVector._view(h)
+
+    @covariances.setter
+    def covariances(self, v):
+        if isinstance(v, Matrix3dVector):
+            v = np.asarray(v)
+        if not D.is_tensor(v):
+            v = np.asarray(v, dtype=np.float64).reshape(-1, 9)
+        a = _Arr.wrap(v, np.float64, 9)
+        self._cov = a if a is not None and len(a) > 0 else None
+
+    def has_covariances(self):
+        return self._cov is not None and len(self._cov) > 0 and len(self._cov) == len(self._xyz)
+
     def has_points(self):
         return len(self._xyz) > 0
 
@@ -268,7 +373,7 @@ class PointCloud:
         return f"PointCloud with {len(self._xyz)} points."
 
     def clear(self):
-        self._xyz, self._rgb, self._nrm = _Arr(host=np.zeros((0, 3))), None, None
+        self._xyz, self._rgb, self._nrm, self._cov = _Arr(host=np.zeros((0, 3))), None, None, None
         return self
 
     def get_min_bound(self):
@@ -306,6 +411,7 @@ class PointCloud:
         self._xyz = _Arr(dev=oxyz)
         if onrm is not None:
             self._nrm = _Arr(dev=onrm)
+        self._cov = None  # covariances are not carried through a transform: estimate them again
         return self
 
     def rotate(self, R, center=None):
@@ -341,7 +447,7 @@ class PointCloud:
         """copy.deepcopy(pcd) (eval_cone.py:84): an independent cloud."""
         out = PointCloud()
         cp = lambda a: a.copy() if a is not None else None
-        out._xyz, out._rgb, out._nrm = cp(self._xyz), cp(self._rgb), cp(self._nrm)
+        out._xyz, out._rgb, out._nrm, out._cov = cp(self._xyz), cp(self._rgb), cp(self._nrm), cp(self._cov)
         memo[id(self)] = out
         return out
 
@@ -475,6 +581,88 @@ class PointCloud:
         L.call("ot_compute_point_cloud_distance", D.ptr(self._xyz.dev()), n,
                D.ptr(target._xyz.dev()) if m else None, m, D.ptr(out), D.stream_ptr())
         return DoubleVector(D.to_host(out))
+
+    # --- normals (DESIGN.md §4 "normals") ---
+    def estimate_covariances(self, search_param=None):
+        """PointCloud::EstimateCovariances — ot_estimate_covariances: per point the covariance of its neighbours
+        (the first knn / max_nn points by (distance, index), hybrid: those inside the radius), stored in
+        `covariances`.  KDTreeSearchParamRadius is refused."""
+        knn, radius = _search_args("EstimateCovariances",
+                                   KDTreeSearchParamKNN() if search_param is None else search_param)
+        n = len(self._xyz)
+        if n == 0:
+            return None
+        cov = D.empty((n, 9), "float64")
+        L.call("ot_estimate_covariances", D.ptr(self._xyz.dev()), n, knn, radius, D.ptr(cov), D.stream_ptr())
+        self._cov = _Arr(dev=cov)
+        return None
+
+    @staticmethod
+    def estimate_point_covariances(input, search_param=None):
+        """PointCloud::EstimatePerPointCovariances: the covariances of `input` as a Matrix3dVector; the cloud is left
+        unchanged."""
+        knn, radius = _search_args("EstimatePerPointCovariances",
+                                   KDTreeSearchParamKNN() if search_param is None else search_param)
+        n = len(input._xyz)
+        if n == 0:
+            return Matrix3dVector()
+        cov = D.empty((n, 9), "float64")
+        L.call("ot_estimate_covariances", D.ptr(input._xyz.dev()), n, knn, radius, D.ptr(cov), D.stream_ptr())
+        return Matrix3dVector._view(D.to_host(cov))
+
+    def estimate_normals(self, search_param=None, fast_normal_computation=True):
+        """PointCloud::EstimateNormals — ot_estimate_normals: the covariances above (stored too), then Open3D's
+        analytic FastEigen3x3 eigenvector of the smallest eigenvalue.  Existing normals orient the new ones (negated
+        when the dot product is negative) and replace a zero result; without them a zero result is (0, 0, 1).  Only
+        the analytic solver is built: fast_normal_computation=False is refused."""
+        knn, radius = _search_args("EstimateNormals", KDTreeSearchParamKNN() if search_param is None else search_param)
+        if not fast_normal_computation:
+            raise RuntimeError("[EstimateNormals] fast_normal_computation=False (the iterative eigen solver) is not "
+                               "built; only Open3D's analytic solver is")
+        n = len(self._xyz)
+        if n == 0:
+            return None
+        prior = self._nrm.dev() if self.has_normals() and len(self._nrm) == n else None
+        nrm, cov = D.empty((n, 3), "float64"), D.empty((n, 9), "float64")
+        L.call("ot_estimate_normals", D.ptr(self._xyz.dev()), n, knn, radius, D.ptr(prior), D.ptr(nrm), D.ptr(cov),
+               D.stream_ptr())
+        self._nrm, self._cov = _Arr(dev=nrm), _Arr(dev=cov)
+        return None
+
+    def _normals_in_place(self, who):
+        """The device normals, about to be rewritten in place (the host copy is dropped afterwards)."""
+        if not self.has_normals():
+            raise RuntimeError(f"[{who}] No normals in the PointCloud. Call EstimateNormals() first.")
+        return self._nrm.dev()
+
+    def normalize_normals(self):
+        """PointCloud::NormalizeNormals — ot_normalize_normals, in place.  Returns self."""
+        if not self.has_normals():
+            return self
+        nrm = self._normals_in_place("NormalizeNormals")
+        L.call("ot_normalize_normals", D.ptr(nrm), len(self._nrm), D.stream_ptr())
+        self._nrm = _Arr(dev=nrm)
+        return self
+
+    def _orient(self, who, mode, ref):
+        ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).reshape(3))
+        nrm = self._normals_in_place(who)
+        n = len(self._nrm)
+        if n != len(self._xyz):
+            raise RuntimeError(f"[{who}] {n} normals for {len(self._xyz)} points")
+        L.call("ot_orient_normals", D.ptr(nrm), D.ptr(self._xyz.dev()), n, mode, ref.ctypes.data_as(L._pd),
+               D.stream_ptr())
+        self._nrm = _Arr(dev=nrm)
+
+    def orient_normals_to_align_with_direction(self, orientation_reference=(0.0, 0.0, 1.0)):
+        """PointCloud::OrientNormalsToAlignWithDirection — ot_orient_normals mode 0: a zero normal becomes the
+        reference, any other is negated when it points against it."""
+        self._orient("OrientNormalsToAlignWithDirection", 0, orientation_reference)
+
+    def orient_normals_towards_camera_location(self, camera_location=(0.0, 0.0, 0.0)):
+        """PointCloud::OrientNormalsTowardsCameraLocation — ot_orient_normals mode 1: per point the reference is
+        camera_location - point."""
+        self._orient("OrientNormalsTowardsCameraLocation", 1, camera_location)
 
     def _select_dev(self, idx):
         out = PointCloud()
