@@ -490,6 +490,44 @@ ot_status ot_mesh_sample_points_min_z_async(const ot_mesh_sample_job* jobs_host,
                                             uint64_t seed, double z_min, void* stream);
 ot_status ot_mesh_sample_points_min_z_wait(int32_t n_jobs, int64_t* n_kept_host);
 
+/* Connected components and triangle clean-up ("mesh components").  Every pointer is a device pointer
+ * unless its name ends in _host.  Every entry checks its arguments before any device work (NULL buffers, negative
+ * sizes, 3 n_triangles or n_vertices beyond 31 bits: OT_ERR_INVALID_ARGUMENT), and every entry that takes n_vertices
+ * first checks the triangle array alone: an index outside [0, n_vertices) gives OT_ERR_INVALID_ARGUMENT ("triangle
+ * index out of range") before that index addresses anything.  All synchronise `stream`.
+ *
+ * mesh.cluster_connected_triangles() — TriangleMesh::ClusterConnectedTriangles.  Triangle (a, b, c) has the edge keys
+ * (min, max) of (a, b), (b, c), (c, a), (a, a) of a degenerate triangle included; two triangles are adjacent when they
+ * share an edge key (sharing one vertex only is not adjacency); the clusters are the connected components of that
+ * adjacency, numbered 0 .. C-1 by ascending smallest triangle index (the labels of Open3D's index-order fill).
+ * out_triangle_clusters [T]; out_cluster_n_triangles [capacity T], the first C written; out_cluster_area [capacity T]
+ * (NULL exactly when vertices is NULL: no areas), the first C written: the float64 sum of the cluster's triangle areas
+ * (TriangleMesh::GetTriangleArea) in an association fixed by the cluster's size, over its triangles in ascending
+ * index order -- the same bits from call to call; a cluster of one triangle gets that triangle's area unchanged. */
+ot_status ot_mesh_cluster_connected_triangles(const int32_t* triangles, int64_t n_triangles,
+                                              const double* vertices /* nullable */, int64_t n_vertices,
+                                              int32_t* out_triangle_clusters, int32_t* out_cluster_n_triangles,
+                                              double* out_cluster_area /* nullable */, int64_t* n_clusters_host,
+                                              void* stream);
+/* mesh.remove_degenerate_triangles(): out_remove_mask[t] = 1 when two of the triangle's three indices are equal,
+ * else 0. */
+ot_status ot_mesh_flag_degenerate_triangles(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                                            uint8_t* out_remove_mask /* [T] */, void* stream);
+/* mesh.remove_duplicated_triangles(): the canonical key of (t0, t1, t2) is, if t0 <= t1, (t0, t1, t2) when t0 <= t2
+ * else (t2, t0, t1); otherwise (t1, t2, t0) when t1 <= t2 else (t2, t0, t1).  out_remove_mask[t] = 1 when an earlier
+ * triangle has the same key, else 0 (rotations are duplicates, flips are not). */
+ot_status ot_mesh_flag_duplicated_triangles(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                                            uint8_t* out_remove_mask /* [T] */, void* stream);
+/* mesh.remove_triangles_by_mask(mask): the triangles whose mask byte is 0, in order, into out_triangles (room for T
+ * rows, must not alias triangles); *n_kept_host their number. */
+ot_status ot_mesh_remove_triangles_by_mask(const int32_t* triangles, int64_t n_triangles, const uint8_t* remove_mask,
+                                           int32_t* out_triangles, int64_t* n_kept_host, void* stream);
+/* mesh.remove_unreferenced_vertices(): out_kept_old_index [capacity V] receives, ascending, the vertices that occur in
+ * some triangle (*n_kept_host of them); the triangle indices are rewritten IN PLACE to the new numbering.  The caller
+ * gathers vertices, colours and normals by that index (ot_gather_rows3). */
+ot_status ot_mesh_remove_unreferenced_vertices(int64_t n_vertices, int32_t* triangles_inout, int64_t n_triangles,
+                                               int32_t* out_kept_old_index, int64_t* n_kept_host, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Hybrid map — fusion/hybrid_map.py
  * ------------------------------------------------------------------------------------------------- */

@@ -118,6 +118,11 @@ SIGNATURES = {
     "ot_mesh_sample_points_min_z_wait": [_i32, _pi64],
     "ot_mesh_sample_points_uniformly_after": [_p, _i32, _i64, C.c_uint64, _p, _p],
     "ot_mesh_get_surface_area": [_p, _i64, _p, _i64, C.POINTER(C.c_double), _p],
+    "ot_mesh_cluster_connected_triangles": [_p, _i64, _p, _i64, _p, _p, _p, _pi64, _p],
+    "ot_mesh_flag_degenerate_triangles": [_p, _i64, _i64, _p, _p],
+    "ot_mesh_flag_duplicated_triangles": [_p, _i64, _i64, _p, _p],
+    "ot_mesh_remove_triangles_by_mask": [_p, _i64, _p, _p, _pi64, _p],
+    "ot_mesh_remove_unreferenced_vertices": [_i64, _p, _i64, _p, _pi64, _p],
     "ot_occupancy_to_points": [_p, _i32, _i32, _i32, _d, _d, _d, _p, _pi64, _p],
     "ot_grid_smart_paste": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _pi64, _p],
     "ot_voxel_key_diff": [_p, _i64, _p, _i64, _d, _p, _p, _pi64, _p, _pi64, _p],

@@ -28,6 +28,7 @@
 
 #include "compact.h"
 #include "grid.h"
+#include "union_find.h"
 
 namespace ot {
 
@@ -59,36 +60,7 @@ __global__ __launch_bounds__(256) void k_db_core(GridDev g, int64_t n, double r2
     minidx[j] = INT_MAX;
 }
 
-__device__ inline int uf_load(int* parent, int x) {
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// parent[x] <= x, and < x for every hooked x: the walk strictly descends, so it ends after at most x steps
-__device__ inline int uf_find(int* parent, int x) {
-    int p = uf_load(parent, x);
-    while (p != x) {
-        x = p;
-        p = uf_load(parent, x);
-    }
-    return x;
-}
-// unite the sets of a and b; returns the root both now share (as far as this lane has seen)
-__device__ inline int uf_union(int* parent, int a, int b) {
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return a;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        int expect = a;  // a > b: hook root a under b, unless another lane hooked a first (then start again from a)
-        if (__hip_atomic_compare_exchange_strong(parent + a, &expect, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            return b;
-    }
-}
-
+// (uf_load / uf_find / uf_union: union_find.h)
 __global__ __launch_bounds__(256) void k_db_hook(GridDev g, int64_t n, double r2,
                                                  const unsigned char* __restrict__ core, int* parent) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -895,6 +895,107 @@ class TriangleMesh:
                D.ptr(self._t.dev()) if nt else None, nt, C.byref(out), D.stream_ptr())
         return out.value
 
+    # --- connected components and triangle clean-up (DESIGN.md §4 "mesh components") ---
+    def cluster_connected_triangles(self):
+        """TriangleMesh::ClusterConnectedTriangles — ot_mesh_cluster_connected_triangles.  Returns (triangle_clusters,
+        cluster_n_triangles, cluster_area): the cluster of each triangle (IntVector, clusters numbered by ascending
+        smallest triangle index), each cluster's size (list of ints) and each cluster's area (DoubleVector)."""
+        self._settle()
+        nt, nv = len(self._t), len(self._v)
+        if nt == 0:
+            return IntVector(), [], DoubleVector()
+        labels = D.empty((nt,), "int32")
+        counts = D.empty((nt,), "int32")
+        areas = D.empty((nt,), "float64") if nv else None  # (triangles without vertices: the range check refuses them)
+        k = C.c_int64(0)
+        L.call("ot_mesh_cluster_connected_triangles", D.ptr(self._t.dev()), nt, D.ptr(self._v.dev()) if nv else None,
+               nv, D.ptr(labels), D.ptr(counts), D.ptr(areas), C.byref(k), D.stream_ptr())
+        c = k.value
+        return IntVector(D.to_host(labels).tolist()), D.to_host(counts[:c]).tolist(), DoubleVector(D.to_host(areas[:c]))
+
+    def _replace_triangles(self, remove_mask_dev):
+        """Keep the triangles whose mask byte is 0, in order (ot_mesh_remove_triangles_by_mask).  The arrays are no
+        longer an extraction's afterwards: compute_vertex_normals takes the generic path."""
+        nt = len(self._t)
+        out = D.empty((nt, 3), "int32")
+        k = C.c_int64(0)
+        L.call("ot_mesh_remove_triangles_by_mask", D.ptr(self._t.dev()), nt, D.ptr(remove_mask_dev), D.ptr(out),
+               C.byref(k), D.stream_ptr())
+        self._t = _Arr(dev=out[:k.value])
+        self._mc = None
+        return self
+
+    def remove_triangles_by_mask(self, triangle_mask):
+        """TriangleMesh::RemoveTrianglesByMask: removes the triangles whose mask entry is true, keeps the rest in
+        order.  Vertices, colours and normals are untouched."""
+        mask = np.asarray(triangle_mask).reshape(-1).astype(bool)
+        if len(mask) != len(self._t):
+            raise RuntimeError("[RemoveTrianglesByMask] triangle_mask needs to have same size as triangles_.")
+        self._settle()
+        if len(mask) == 0:
+            self._mc = None
+            return self
+        return self._replace_triangles(D.to_device(mask.astype(np.uint8)))
+
+    def remove_triangles_by_index(self, triangle_indices):
+        """TriangleMesh::RemoveTrianglesByIndex: the same through a mask; indices outside [0, T) are ignored and
+        repeats are harmless."""
+        nt = len(self._t)
+        idx = np.asarray(triangle_indices, dtype=np.int64).reshape(-1)
+        mask = np.zeros(nt, bool)
+        mask[idx[(idx >= 0) & (idx < nt)]] = True
+        return self.remove_triangles_by_mask(mask)
+
+    def _remove_flagged(self, entry):
+        self._settle()
+        nt = len(self._t)
+        if nt == 0:
+            self._mc = None
+            return self
+        mask = D.empty((nt,), "uint8")
+        L.call(entry, D.ptr(self._t.dev()), nt, len(self._v), D.ptr(mask), D.stream_ptr())
+        return self._replace_triangles(mask)
+
+    def remove_degenerate_triangles(self):
+        """TriangleMesh::RemoveDegenerateTriangles: removes a triangle when any two of its three indices are equal
+        (ot_mesh_flag_degenerate_triangles, then the mask removal)."""
+        return self._remove_flagged("ot_mesh_flag_degenerate_triangles")
+
+    def remove_duplicated_triangles(self):
+        """TriangleMesh::RemoveDuplicatedTriangles: removes a triangle when an earlier one has the same canonical
+        rotation (ot_mesh_flag_duplicated_triangles): rotations are duplicates, flips are not; the survivor keeps its
+        own index order."""
+        return self._remove_flagged("ot_mesh_flag_duplicated_triangles")
+
+    def remove_unreferenced_vertices(self):
+        """TriangleMesh::RemoveUnreferencedVertices: keeps the vertices that occur in some triangle, in order, with
+        their colours and normals, and rewrites the triangle indices (ot_mesh_remove_unreferenced_vertices)."""
+        self._settle()
+        nv, nt = len(self._v), len(self._t)
+        self._mc = None
+        if nv == 0:
+            return self
+        tri = self._t.dev().clone() if nt else None  # rewritten in place: the mesh's own copy stays whole on an error
+        kept = D.empty((nv,), "int32")
+        k = C.c_int64(0)
+        L.call("ot_mesh_remove_unreferenced_vertices", nv, D.ptr(tri), nt, D.ptr(kept), C.byref(k), D.stream_ptr())
+        m = k.value
+        idx = kept[:m].to(D.torch.int64)
+
+        def g(a):
+            o = D.empty((m, 3), "float64")
+            if m:
+                L.call("ot_gather_rows3", D.ptr(a.dev()), D.ptr(idx), m, D.ptr(o), D.stream_ptr())
+            return _Arr(dev=o)
+
+        vc = g(self._vc) if self.has_vertex_colors() and len(self._vc) == nv else self._vc
+        vn = g(self._vn) if self.has_vertex_normals() and len(self._vn) == nv else self._vn
+        self._v = g(self._v)
+        self._vc, self._vn = vc, vn
+        if nt:
+            self._t = _Arr(dev=tri)
+        return self
+
     def sample_points_uniformly(self, number_of_points=100, use_triangle_normal=False, seed=0):
         """TriangleMesh::SamplePointsUniformly (reconstruct_rgbd_filter.py:123) with a seeded counter RNG."""
         if number_of_points <= 0:
