@@ -266,7 +266,9 @@ ot_status ot_tsdf_set_batch(ot_tsdf* vol, int32_t max_frames);
  * a second stream of the volume (two staging sets); readers (num_units, export, extraction, flush, reset) order the
  * caller's stream after the last integrate.  -1 (default): on for spatially sharded volumes (their split front end
  * stages only their units' tiles; measured faster at 2, 4 and 8 ranks), off otherwise; 0 off; 1 on.
- * Results are identical in every mode.  Fails with OT_ERR_INVALID_ARGUMENT while frames are queued (flush on their stream first). */
+ * Results are identical in every mode.  Fails with OT_ERR_INVALID_ARGUMENT while frames are queued (flush on their stream first).
+ * A batch whose integrate is still deferred (sharded volumes from 4 ranks) need not be flushed first: the next batch
+ * launches it before it restages anything. */
 ot_status ot_tsdf_set_frontend_overlap(ot_tsdf* vol, int32_t mode);
 
 /* Batch statistics since the last reset (measurement; not an Open3D API): integrate batches run, the units they touched

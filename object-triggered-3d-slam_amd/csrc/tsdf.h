@@ -117,6 +117,31 @@ __device__ inline void note_unit_key(const TsdfDev& d, int x, int y, int z) {
     }
 }
 
+__device__ inline int hash_insert(const TsdfDev& d, unsigned long long key) {
+    unsigned slot = (unsigned)mix64(key) & (unsigned)d.hash_mask;
+    for (int probe = 0; probe <= d.hash_mask; ++probe) {
+        const unsigned long long k = d.hkeys[slot];
+        if (k == key) return (int)slot;
+        if (k == KEY_EMPTY) {
+            const unsigned long long old = atomicCAS(&d.hkeys[slot], KEY_EMPTY, key);
+            if (old == KEY_EMPTY || old == key) return (int)slot;
+        }
+        slot = (slot + 1) & (unsigned)d.hash_mask;
+    }
+    return -1;
+}
+
+__device__ inline int hash_find(const TsdfDev& d, unsigned long long key) {
+    unsigned slot = (unsigned)mix64(key) & (unsigned)d.hash_mask;
+    for (int probe = 0; probe <= d.hash_mask; ++probe) {
+        const unsigned long long k = d.hkeys[slot];
+        if (k == key) return (int)slot;
+        if (k == KEY_EMPTY) return -1;
+        slot = (slot + 1) & (unsigned)d.hash_mask;
+    }
+    return -1;
+}
+
 // a unit's record: tsdf plane, weight plane, then the colour planes r, g, b (4096 each, voxel vi = z*256 + x*16 + y)
 // in float32 or, when the volume keeps colour at Open3D's precision, float64 (the record is then 128 KiB)
 __host__ __device__ inline float* unit_base(const TsdfDev& d, int id) { return d.vox + (size_t)id * d.unit_floats; }
@@ -160,6 +185,78 @@ struct BatchFrame {
     float es[3];              // column 2 of (float)extrinsic * voxel_length
     float scale;              // (float)depth_scale
     double trunc;             // depth_trunc
+};
+
+// parameters of the integrate kernels (tsdf.hip make_integrate_params)
+struct IntegrateParams {
+    const float* depth;
+    const uint8_t* color;
+    const float* mult;  // the volume's ray-multiplier table [H][W]: gathered by the lanes that can update
+    int W, H;
+    float fx, fy, cx, cy;
+    float E[12];
+    float es0, es1, es2;
+    float vl, half, trunc, trunc_inv, safe_w, safe_h;
+    float inv_fx, inv_fy;  // (float)(1 / (float)fx) as CreateDepthToCameraDistanceMultiplierFloatImage
+    float proj_eps;  // certified fast projection: |u - rint(u)| > proj_eps decides floor and bounds exactly
+    int rcp_hi;      // FAST kernels: the largest weight + 1 of the batch (frames since reset + the batch's), <= RCP_N
+    double unit_len;
+};
+
+// parameters of the touch kernels (tsdf.hip make_touch_params)
+struct BatchTouchParams {
+    int W, stride, ws, hs;
+    double fx, fy, cx, cy;
+    double trunc, unit_len;
+    double inv_unit;    // RN(1 / unit_len): floor_div's certified product
+    int slot_cap;
+    int64_t npx;        // pixels per frame (fused staging: k_batch_touch stages the batch's pixels too)
+    int pc;             // this batch's pair counter index
+    int tiles;          // touch workgroups per frame group (blockIdx.x below it)
+    int stage_blocks;   // staging-only workgroups per frame group after them (0: each touch workgroup stages a share)
+    int tf;             // frames per group (TF)
+    int sample_stage;   // split front end (stage_blocks < 0): each stride sample stores its own pixel's staged record
+                        // (a replay touch reads it; k_stage_tiles stages only the owned units' footprints)
+};
+
+// parameters of the split front end's tile-mask kernel (tsdf.hip make_stage_params)
+struct StageMaskParams {
+    int W, H, tiles_x, tiles_y, wpr;  // wpr: 32-bit mask words per tile row
+    float fx, fy, cx, cy, vl, half;
+    double unit_len;
+    int nframes;
+};
+
+// an entry of a batch's work list (k_batch_units -> the integrate)
+struct UnitWork {
+    int id;                   // pool id, | 0x80000000 when fresh (state starts at zero), -1 when dropped
+    int kx, ky, kz;           // unit key
+    unsigned long long mask;  // frames of the batch that touch the unit (bit f = frame f)
+    unsigned long long pad;
+};
+
+// How a batch runs (tsdf.hip plan_batch chooses once per batch; everything after it reads the plan):
+//   Direct   : front end and integrate on the caller's stream, set 0
+//   Overlap  : double-buffered front end -- the integrate on the volume's integrate stream behind the set's units kernel
+//   Deferred : the integrate waits to be launched with the next batch's touch (k_integrate_touch), or alone
+enum class BatchMode { Direct, Overlap, Deferred };
+struct BatchPlan {
+    BatchMode mode = BatchMode::Direct;
+    bool split = false;     // split front end: touch without staging -> units -> tile mask -> staging of the marked tiles
+    int set = 0;            // the batch's staging set (ot_tsdf::bset; its work list: tsdf.hip set_work -- resolved at each
+                            // launch, pool growth reallocates the lists)
+    int* wcount = nullptr;  // where the integrate reads the work list's length: the batch's pair counter, or ...
+    int* wcopy = nullptr;   // ... the set's copy the units kernel writes (Overlap, Deferred; nullptr: Direct)
+};
+
+// the context a batch's settle, a replay and a deferred launch need
+struct BatchCtx {
+    BatchPlan plan;
+    BatchTouchParams tp;
+    IntegrateParams ip0;
+    StageMaskParams sq{};       // split: a replay stages its units' tiles too (units the full hash dropped were in no
+    unsigned* smask = nullptr;  // work list of the first pass, so their footprints were never staged); the tile masks
+    int n, pc, variant;
 };
 
 struct PendingFrame {
@@ -224,8 +321,8 @@ struct ot_tsdf {
     ot::BatchFrame* hbframes = nullptr;    // pinned host staging [2][MAX_BATCH]
     unsigned* hmail = nullptr;             // pinned coherent host mailbox [OT_MAIL_WORDS]: small read-backs stored
                                            // by a one-wave kernel (mail_words) instead of staged D2H copies
-    // staging half of the next batch; a batch's parameter copy has run once its units kernel has mailed (settle_batch
-    // waits for that before integrate_batch returns), so the halves need no event
+    // staging half of the next batch; a batch's parameter copy has run once its units kernel has mailed (tsdf.hip
+    // settle_batch waits for that before integrate_batch returns), so the halves need no event
     int hb_next = 0;
     // the counters as the last batch's units kernel left them (the integrate does not change them), mailed by its last
     // workgroup to hmail + OT_MAIL_WORDS, then sequence number `units_seq` to word MAIL_SEQ_UNITS: the host spins on
@@ -256,12 +353,13 @@ struct ot_tsdf {
     int tmask_w = 0, tmask_h = 0;  // the image size the masks are laid out for
     int split_mode = -1;          // -1 (default): split for sharded volumes; 0 off; 1 on (test hook)
     // Deferred integrate of a sharded volume's last batch (round 6): its front end ran, its integrate waits to be launched
-    // together with the next batch's touch (k_integrate_touch) or alone by the next flush.  dfr_ctx holds the batch's
-    // context (tsdf.hip BatchCtx), dfr_stream the stream its front end ran on.
+    // together with the next batch's touch (k_integrate_touch) or alone -- by the next flush, or by the next batch when
+    // that one does not fuse (tsdf.hip integrate_batch owns the hand-over).  dfr holds the batch's context while dfr_on,
+    // dfr_stream the stream its front end ran on.
     bool dfr_on = false;
     hipStream_t dfr_stream = nullptr;
-    hipEvent_t ev_dfr = nullptr;  // dfr_stream -> a flush on another stream
-    alignas(16) unsigned char dfr_ctx[1024];
+    hipEvent_t ev_dfr = nullptr;  // dfr_stream -> the next batch or a flush on another stream
+    ot::BatchCtx dfr;
     // batch statistics since reset (ot_tsdf_batch_stats; the bench's compulsory-bytes figure): batches, units touched
     // summed over batches, units new in their batch; units the last batch left (-1: unknown after an import)
     int64_t stat_batches = 0, stat_unit_batches = 0, stat_fresh = 0, stat_prev_units = 0;
@@ -297,7 +395,27 @@ struct ot_tsdf {
 };
 
 namespace ot {
-// shared between tsdf.hip and mc.hip
+// The TSDF test hooks (process-wide; set by the otx_* entry points of tsdf_volume.hip, -1 / false: the default rule).
+struct TsdfHooks {
+    int int_fine = -1;     // otx_integrate_fine: slice form by the batch's size (-1), 0 coarse, 1 fine
+    int fine_units = -1;   // otx_integrate_fine >= 2: the deferred integrate takes the fine slices below this many units
+    int int_depth = -1;    // otx_integrate_depth: frame pipeline depth KT of the fine slices, 1..3
+    int int_wg = -1;       // otx_integrate_workgroup: waves per workgroup of the coarse integrate, 1, 2 or 4
+    int stage_blocks = -1; // otx_touch_stage_blocks: staging-only touch workgroups (-1: two per tile)
+    int touch_tf = -1;     // otx_touch_frames: frames per touch workgroup (-1: TF)
+    int split = -1;        // otx_split_frontend: by the volume (-1), 0 never, 1 always (unsharded too)
+    int defer = -1;        // otx_defer_integrate: by the volume (-1), 0 never, 1 with any split batch
+    bool unit_sort_radix = false;  // otx_unit_sort_radix: the radix sort at every key width
+};
+extern TsdfHooks g_tsdf_hooks;
+
+// the three TSDF translation units share these: tsdf.hip (integrate: kernels and the batch pipeline), tsdf_exchange.hip
+// (unit order, export, import, border halo), tsdf_volume.hip (create, reset, settings, read-outs, hooks)
+// room for `extra` more units before a kernel that allocates up to that many (imports): the pool grows now if needed
+ot_status reserve_units(ot_tsdf* vol, int64_t extra, hipStream_t stream);
+// the units an export lists: every unit in key order or, for a sharded volume, its own
+ot_status export_list(ot_tsdf* vol, hipStream_t stream, const unsigned** ids, int64_t* n);
+// shared with mc.hip
 ot_status tsdf_sorted_units(ot_tsdf* vol, hipStream_t stream, int64_t* n_units);
 // small read-back: the 4-byte words at p[0 .. n) copied to vol->hmail by one kernel, then the stream synchronised
 struct MailSrc {

@@ -13,35 +13,18 @@
 // k_batch_integrate, below.  The unit pool is unbounded like Open3D's: when a batch needs more units than the pool
 // holds, the pool and the hash grow (records copied, keys rehashed) and the batch's dropped units are integrated
 // again from its staged frames (settle_batch), so the result is the one an unbounded pool gives.
+// This file: the touch, units, staging and integrate kernels and the host batch pipeline that launches them
+// (integrate_batch, settle_batch, grow_pool, tsdf_flush).  The unit exchange is tsdf_exchange.hip, the volume's life
+// cycle, settings and read-outs tsdf_volume.hip.
 #include <algorithm>
 #include <cmath>
-#include <sched.h>
-#include <chrono>
-#include <thread>
 #include <cstring>
 #include <type_traits>
 #include <utility>
 
-#include "compact.h"
-#include "sort.h"
 #include "tsdf.h"
 
 namespace ot {
-
-struct IntegrateParams {
-    const float* depth;
-    const uint8_t* color;
-    const float* mult;  // the volume's ray-multiplier table [H][W]: gathered by the lanes that can update
-    int W, H;
-    float fx, fy, cx, cy;
-    float E[12];
-    float es0, es1, es2;
-    float vl, half, trunc, trunc_inv, safe_w, safe_h;
-    float inv_fx, inv_fy;  // (float)(1 / (float)fx) as CreateDepthToCameraDistanceMultiplierFloatImage
-    float proj_eps;  // certified fast projection: |u - rint(u)| > proj_eps decides floor and bounds exactly
-    int rcp_hi;      // FAST kernels: the largest weight + 1 of the batch (frames since reset + the batch's), <= RCP_N
-    double unit_len;
-};
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -61,31 +44,6 @@ __device__ inline void st_f64(__amdgpu_buffer_rsrc_t r, int i, double x) {
     v.x = (unsigned)__double2loint(x);
     v.y = (unsigned)__double2hiint(x);
     __builtin_amdgcn_raw_buffer_store_b64(v, r, i * 8, 0, 0);
-}
-
-__device__ inline int hash_insert(const TsdfDev& d, unsigned long long key) {
-    unsigned slot = (unsigned)mix64(key) & (unsigned)d.hash_mask;
-    for (int probe = 0; probe <= d.hash_mask; ++probe) {
-        const unsigned long long k = d.hkeys[slot];
-        if (k == key) return (int)slot;
-        if (k == KEY_EMPTY) {
-            const unsigned long long old = atomicCAS(&d.hkeys[slot], KEY_EMPTY, key);
-            if (old == KEY_EMPTY || old == key) return (int)slot;
-        }
-        slot = (slot + 1) & (unsigned)d.hash_mask;
-    }
-    return -1;
-}
-
-__device__ inline int hash_find(const TsdfDev& d, unsigned long long key) {
-    unsigned slot = (unsigned)mix64(key) & (unsigned)d.hash_mask;
-    for (int probe = 0; probe <= d.hash_mask; ++probe) {
-        const unsigned long long k = d.hkeys[slot];
-        if (k == key) return (int)slot;
-        if (k == KEY_EMPTY) return -1;
-        slot = (slot + 1) & (unsigned)d.hash_mask;
-    }
-    return -1;
 }
 
 // ============================================================================ batched (temporal blocking)
@@ -203,21 +161,6 @@ __global__ __launch_bounds__(COPY_FRAMES_LANES) void k_copy_frames(const uint4* 
     if (i < n16) dst[i] = src[i];
 }
 
-struct BatchTouchParams {
-    int W, stride, ws, hs;
-    double fx, fy, cx, cy;
-    double trunc, unit_len;
-    double inv_unit;    // RN(1 / unit_len): floor_div's certified product
-    int slot_cap;
-    int64_t npx;        // pixels per frame (fused staging: k_batch_touch stages the batch's pixels too)
-    int pc;             // this batch's pair counter index
-    int tiles;          // touch workgroups per frame group (blockIdx.x below it)
-    int stage_blocks;   // staging-only workgroups per frame group after them (0: each touch workgroup stages a share)
-    int tf;             // frames per group (TF)
-    int sample_stage;   // split front end (stage_blocks < 0): each stride sample stores its own pixel's staged record
-                        // (a replay touch reads it; k_stage_tiles stages only the owned units' footprints)
-};
-
 // floor(RN(a / b)) -- Open3D's LocateVolumeUnit on a float64 quotient -- with one multiply in the common case: v =
 // RN(a * RN(1/b)) is within 2^-52 |a/b| of a/b (and RN(a/b) within 2^-53), so when v lies farther than 1e-14 |v| (+ an
 // absolute floor far below any unit index) from every integer, floor(v) is floor(RN(a/b)); otherwise the IEEE division.
@@ -260,7 +203,6 @@ constexpr int TT = 16;          // tile edge in samples
 // within 0.2 % of 4, a rank of 8 shards 3 % faster -- front end 99 vs 105 us per batch; 8: +10 %); with every touch
 // workgroup staging a share first, 4 was 1 % faster than 2 (round 3)
 constexpr int TF = 2;
-static int g_touch_tf = TF;  // test hook otx_touch_frames: frames per touch workgroup (A/B timing)
 constexpr int LTAB = 1024;   // LDS table entries (16 B each + a 4-B slot in the list of used entries)
 
 __device__ inline bool lds_merge(unsigned long long* keys, unsigned long long* masks, unsigned short* used, int* nused,
@@ -456,13 +398,6 @@ constexpr int SLICES = 4 * (UNIT_RES / BZ);   // waves per unit
 constexpr int INT_WG = 4;
 constexpr int INT_PARTS = SLICES / INT_WG;  // four-wave workgroups per unit
 
-struct UnitWork {
-    int id;                   // pool id, | 0x80000000 when fresh (state starts at zero), -1 when dropped
-    int kx, ky, kz;           // unit key
-    unsigned long long mask;  // frames of the batch that touch the unit (bit f = frame f)
-    unsigned long long pad;
-};
-
 // Unit headers of the batch: allocate new units, move and clear the frame masks (ready for the next batch).  A unit the
 // pool cannot hold is dropped (id -1, C_OVERFLOW; not counted) and integrated by the replay once the pool has grown.
 // REPLAY: units that already have an id were integrated by the batch's first pass: skipped (id -1, not counted).
@@ -610,12 +545,6 @@ __global__ __launch_bounds__(256) void k_batch_units(TsdfDev d, UnitWork* __rest
 // touch (no staging) -> units -> k_stage_mask (the tiles each (owned unit, frame) pair can project to) -> k_stage_tiles
 // (only those tiles).  The staged values are a pure function of the pixel, so staging a superset changes no bit.
 constexpr int STX = 32, STY = 16;  // staging tile: 32 pixels (one 8-lane group of quads per row) x 16 rows
-struct StageMaskParams {
-    int W, H, tiles_x, tiles_y, wpr;  // wpr: 32-bit mask words per tile row
-    float fx, fy, cx, cy, vl, half;
-    double unit_len;
-    int nframes;
-};
 // Footprint of a unit in a frame: the voxel centres span the box [p(0), p(15)] per axis (the integrate's own float
 // expressions for x, y = 0 and 15; z from the unit origin by 15 voxel lengths), so in exact arithmetic their projections
 // lie in the projected corners' bounding box (the box is in front of the camera).  The integrate's float projection of a
@@ -1319,316 +1248,6 @@ __global__ __launch_bounds__(64 * INT_WG, (C64 && !FAST) ? 5 : 4) void k_integra
     }
 }
 
-// export: units in sorted order, voxels transposed to Open3D IndexOf order (x*256 + y*16 + z); colour as CT
-// (float export of a float64 volume rounds to nearest)
-template <typename CT, typename OT>
-__global__ __launch_bounds__(256) void k_export(TsdfDev d, const unsigned* sorted_ids, int32_t* keys, float* tsdf,
-                                                float* weight, OT* color) {
-    const int r = blockIdx.x;
-    const int id = (int)sorted_ids[r];
-    const int tid = threadIdx.x;
-    const float* base = unit_base(d, id);
-    const CT* cbase = color_base<CT>(d, id);
-    if (keys && tid < 3) keys[(int64_t)r * 3 + tid] = d.unit_keys[id * 3 + tid];
-    for (int z = 0; z < UNIT_RES; ++z) {
-        const int vi = z * 256 + tid;
-        const int64_t o = (int64_t)r * UNIT_VOX + tid * 16 + z;
-        if (tsdf) tsdf[o] = base[vi];
-        if (weight) weight[o] = base[UNIT_VOX + vi];
-        if (color) {
-            color[o * 3 + 0] = (OT)cbase[vi];
-            color[o * 3 + 1] = (OT)cbase[UNIT_VOX + vi];
-            color[o * 3 + 2] = (OT)cbase[2 * UNIT_VOX + vi];
-        }
-    }
-}
-
-// border export: the BORDER_VOX low-face voxels of every unit, units in sorted order; colour as the volume keeps it
-template <typename CT>
-__global__ __launch_bounds__(256) void k_export_border(TsdfDev d, const unsigned* sorted_ids, int32_t* keys,
-                                                       float* tsdf, float* weight, CT* color) {
-    const int r = blockIdx.x;
-    const int id = (int)sorted_ids[r];
-    const float* base = unit_base(d, id);
-    const CT* cbase = color_base<CT>(d, id);
-    if (threadIdx.x < 3) keys[(int64_t)r * 3 + threadIdx.x] = d.unit_keys[id * 3 + threadIdx.x];
-    for (int b = threadIdx.x; b < BORDER_VOX; b += 256) {
-        int x, y, z;
-        border_voxel(b, x, y, z);
-        const int vi = z * 256 + x * 16 + y;
-        const int64_t o = (int64_t)r * BORDER_VOX + b;
-        tsdf[o] = base[vi];
-        weight[o] = base[UNIT_VOX + vi];
-        if (color) {
-            color[o * 3 + 0] = cbase[vi];
-            color[o * 3 + 1] = cbase[UNIT_VOX + vi];
-            color[o * 3 + 2] = cbase[2 * UNIT_VOX + vi];
-        }
-    }
-}
-
-__device__ inline int find_unit_id(const TsdfDev& d, int x, int y, int z) {
-    if (!key_in_range(x, y, z)) return -1;
-    const unsigned long long key = pack_key(x, y, z);
-    unsigned slot = (unsigned)mix64(key) & (unsigned)d.hash_mask;
-    for (int probe = 0; probe <= d.hash_mask; ++probe) {
-        const unsigned long long k = d.hkeys[slot];
-        if (k == key) {
-            const int id = d.hvals[slot];
-            return id < d.max_units ? id : -1;
-        }
-        if (k == KEY_EMPTY) return -1;
-        slot = (slot + 1) & (unsigned)d.hash_mask;
-    }
-    return -1;
-}
-
-// border import (halo): a row becomes a halo unit of this volume when its key is not owned here and one of its
-// -x/-y/-z neighbours (the units whose marching cubes read it) is; a new halo unit is zeroed (weight 0 = unobserved)
-// and receives the border voxels.  Rows of owned or unneeded units are skipped.
-template <typename CT>
-__global__ __launch_bounds__(256) void k_import_border(TsdfDev d, const int32_t* __restrict__ keys,
-                                                       const float* __restrict__ tsdf, const float* __restrict__ weight,
-                                                       const CT* __restrict__ color) {
-    __shared__ int s_id, s_fresh;
-    const int r = blockIdx.x;
-    if (threadIdx.x == 0) {
-        const int x = keys[(int64_t)r * 3], y = keys[(int64_t)r * 3 + 1], z = keys[(int64_t)r * 3 + 2];
-        int id = -1, fresh = 0;
-        bool needed = false;
-        if (key_in_range(x, y, z) && !unit_owned(d, pack_key(x, y, z))) {
-            for (int t = 1; t < 8 && !needed; ++t) {
-                const int nx = x - ((t >> 2) & 1), ny = y - ((t >> 1) & 1), nz = z - (t & 1);
-                needed = key_in_range(nx, ny, nz) && unit_owned(d, pack_key(nx, ny, nz)) &&
-                         find_unit_id(d, nx, ny, nz) >= 0;
-            }
-        }
-        if (needed) {
-            const int slot = hash_insert(d, pack_key(x, y, z));
-            if (slot < 0) {
-                atomicOr(&d.counters[C_HASHERR], 1);
-            } else {
-                id = d.hvals[slot];
-                if (id < 0) {
-                    id = atomicAdd(&d.counters[C_UNITS], 1);
-                    if (id >= d.max_units) {
-                        atomicOr(&d.counters[C_OVERFLOW], 1);
-                        id = -1;
-                    } else {
-                        d.hvals[slot] = id;
-                        d.unit_keys[id * 3 + 0] = x;
-                        d.unit_keys[id * 3 + 1] = y;
-                        d.unit_keys[id * 3 + 2] = z;
-                        fresh = 1;
-                        note_unit_key(d, x, y, z);
-                    }
-                }
-            }
-        }
-        s_id = id;
-        s_fresh = fresh;
-    }
-    __syncthreads();
-    const int id = s_id;
-    if (id < 0) return;
-    float* base = unit_base(d, id);
-    CT* cbase = color_base<CT>(d, id);
-    if (s_fresh) {
-        for (int vi = threadIdx.x; vi < UNIT_VOX; vi += 256) {
-            base[vi] = 0.0f;
-            base[UNIT_VOX + vi] = 0.0f;
-            cbase[vi] = cbase[UNIT_VOX + vi] = cbase[2 * UNIT_VOX + vi] = (CT)0;
-        }
-        __syncthreads();
-    }
-    for (int b = threadIdx.x; b < BORDER_VOX; b += 256) {
-        int x, y, z;
-        border_voxel(b, x, y, z);
-        const int vi = z * 256 + x * 16 + y;
-        const int64_t o = (int64_t)r * BORDER_VOX + b;
-        base[vi] = tsdf[o];
-        base[UNIT_VOX + vi] = weight[o];
-        cbase[vi] = color ? color[o * 3 + 0] : (CT)0;
-        cbase[UNIT_VOX + vi] = color ? color[o * 3 + 1] : (CT)0;
-        cbase[2 * UNIT_VOX + vi] = color ? color[o * 3 + 2] : (CT)0;
-    }
-}
-
-// destinations of a border row (SURVEY §8(e) halo): the ranks owning the unit's 7 -x/-y/-z neighbours (the units whose
-// marching cubes read its low faces), this rank excluded -- a superset of the rows k_import_border keeps there
-__global__ __launch_bounds__(256) void k_border_dest(TsdfDev d, int64_t n, const int32_t* __restrict__ keys,
-                                                     unsigned long long* __restrict__ mask) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n) return;
-    const int x = keys[r * 3], y = keys[r * 3 + 1], z = keys[r * 3 + 2];
-    unsigned long long m = 0ull;
-    if (d.shard_world > 1)
-        for (int t = 1; t < 8; ++t) {
-            const int nx = x - ((t >> 2) & 1), ny = y - ((t >> 1) & 1), nz = z - (t & 1);
-            if (key_in_range(nx, ny, nz)) m |= 1ull << unit_owner(d, nx, ny, nz);
-        }
-    mask[r] = m & ~(1ull << d.shard_rank);
-}
-
-// owned units of the sorted order (a sharded volume's own units; every unit when unsharded)
-struct OwnedPred {
-    TsdfDev d;
-    const unsigned* sorted_ids;
-    __device__ bool operator()(int64_t r) const {
-        const int id = (int)sorted_ids[r];
-        return d.shard_world <= 1 ||
-               unit_owned(d, pack_key(d.unit_keys[id * 3], d.unit_keys[id * 3 + 1], d.unit_keys[id * 3 + 2]));
-    }
-};
-struct OwnedEmit {
-    const unsigned* sorted_ids;
-    unsigned* out;
-    __device__ void operator()(int64_t r, int64_t pos) const { out[pos] = sorted_ids[r]; }
-};
-
-// Units an export lists: every unit in sorted key order or, for a spatially sharded volume, only its own units -- the
-// halo units imported for marching cubes (k_import_border) are copies of other shards' border rows, and exporting
-// them would hand their keys to an assembly twice (the second time with zeros inside the unit).
-static ot_status export_list(ot_tsdf* vol, hipStream_t stream, const unsigned** ids, int64_t* n) {
-    int64_t nu = 0;
-    ot_status st = tsdf_sorted_units(vol, stream, &nu);
-    if (st != OT_OK) return st;
-    *ids = vol->sorted_ids;
-    *n = nu;
-    if (vol->dev.shard_world <= 1 || nu == 0) return OT_OK;
-    unsigned* own = (unsigned*)scratch(sizeof(unsigned) * (size_t)nu + 256, 16);
-    if (!own) return fail(OT_ERR_HIP, "scratch allocation failed");
-    int64_t no = 0;
-    st = compact(nu, OwnedPred{vol->dev, vol->sorted_ids}, OwnedEmit{vol->sorted_ids, own}, stream, &no, 13);
-    if (st != OT_OK) return st;
-    *ids = own;
-    *n = no;
-    return OT_OK;
-}
-
-// import: the inverse of k_export (keys unique within one call; an existing unit is overwritten); colour as the
-// volume keeps it (CT)
-template <typename CT>
-__global__ __launch_bounds__(256) void k_import(TsdfDev d, const int32_t* __restrict__ keys,
-                                                const float* __restrict__ tsdf, const float* __restrict__ weight,
-                                                const CT* __restrict__ color) {
-    __shared__ int s_id;
-    const int r = blockIdx.x;
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        const int x = keys[(int64_t)r * 3], y = keys[(int64_t)r * 3 + 1], z = keys[(int64_t)r * 3 + 2];
-        int id = -1;
-        if (!key_in_range(x, y, z)) {
-            atomicOr(&d.counters[C_HASHERR], 2);
-        } else {
-            const int slot = hash_insert(d, pack_key(x, y, z));
-            if (slot < 0) {
-                atomicOr(&d.counters[C_HASHERR], 1);
-            } else {
-                id = d.hvals[slot];
-                if (id < 0) {
-                    id = atomicAdd(&d.counters[C_UNITS], 1);
-                    if (id >= d.max_units) {
-                        atomicOr(&d.counters[C_OVERFLOW], 1);
-                        id = -1;
-                    } else {
-                        d.hvals[slot] = id;
-                        d.unit_keys[id * 3 + 0] = x;
-                        d.unit_keys[id * 3 + 1] = y;
-                        d.unit_keys[id * 3 + 2] = z;
-                        note_unit_key(d, x, y, z);
-                    }
-                }
-            }
-        }
-        s_id = id;
-    }
-    __syncthreads();
-    const int id = s_id;
-    if (id < 0) return;
-    float* base = unit_base(d, id);
-    CT* cbase = color_base<CT>(d, id);
-    for (int z = 0; z < UNIT_RES; ++z) {
-        const int vi = z * 256 + tid;
-        const int64_t o = (int64_t)r * UNIT_VOX + tid * 16 + z;
-        base[vi] = tsdf[o];
-        base[UNIT_VOX + vi] = weight[o];
-        cbase[vi] = color ? color[o * 3 + 0] : (CT)0;
-        cbase[UNIT_VOX + vi] = color ? color[o * 3 + 1] : (CT)0;
-        cbase[2 * UNIT_VOX + vi] = color ? color[o * 3 + 2] : (CT)0;
-    }
-}
-
-// order-preserving compact keys: (x - x0) << (by + bz) | (y - y0) << bz | (z - z0), only the bits the ranges need
-struct UnitKeyPack {
-    int x0, y0, z0, sy, sx;
-};
-
-__global__ void k_pack_unit_keys(TsdfDev d, int n, UnitKeyPack pk, unsigned long long* keys, unsigned* ids) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = ((unsigned long long)(d.unit_keys[i * 3 + 0] - pk.x0) << pk.sx) |
-              ((unsigned long long)(d.unit_keys[i * 3 + 1] - pk.y0) << pk.sy) |
-              (unsigned long long)(d.unit_keys[i * 3 + 2] - pk.z0);
-    ids[i] = (unsigned)i;
-}
-
-// Unit order in ONE launch when the packed keys need <= USORT_BITS bits (a volume a few metres across): unit keys are
-// distinct (one id per hash slot), so a unit's place in key order is the number of smaller keys -- a presence bitmap
-// of the key space in LDS, a block scan of its popcounts per 8-word group, then per unit the group prefix plus the
-// popcounts before its bit.  The same ids as the radix sort (k_pack_unit_keys + 4 launches of sort_pairs_u64_u32),
-// whose launches dominated the unit sort of a single object (38 us for 5.6k units, profiles/r04z_obj_timeline.txt).
-constexpr int USORT_BITS = 20;                   // 2^20-bit bitmap: 128 KiB of LDS
-constexpr int USORT_WORDS = 1 << (USORT_BITS - 5);
-constexpr int USORT_GROUPS = USORT_WORDS / 8;    // 4096 group prefixes: 16 KiB
-__device__ inline unsigned unit_key_bits(const TsdfDev& d, const UnitKeyPack& pk, int i) {
-    return ((unsigned)(d.unit_keys[i * 3 + 0] - pk.x0) << pk.sx) | ((unsigned)(d.unit_keys[i * 3 + 1] - pk.y0) << pk.sy) |
-           (unsigned)(d.unit_keys[i * 3 + 2] - pk.z0);
-}
-__global__ __launch_bounds__(1024) void k_unit_rank_sort(TsdfDev d, int n, UnitKeyPack pk, int kb,
-                                                         unsigned* __restrict__ sorted_ids) {
-    __shared__ unsigned s_bits[USORT_WORDS];
-    __shared__ unsigned s_gp[USORT_GROUPS];
-    __shared__ unsigned s_w[16];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int words = kb > 5 ? 1 << (kb - 5) : 1, groups = (words + 7) >> 3;
-    for (int q = t; q < words; q += 1024) s_bits[q] = 0u;
-    __syncthreads();
-    for (int i = t; i < n; i += 1024) {
-        const unsigned k = unit_key_bits(d, pk, i);
-        atomicOr(&s_bits[k >> 5], 1u << (k & 31));
-    }
-    __syncthreads();
-    // thread t: groups [g0, g1), a contiguous stretch (4 groups = 32 words at 20 bits)
-    const int per = (groups + 1023) >> 10, g0 = t * per, g1 = g0 + per < groups ? g0 + per : groups;
-    unsigned loc = 0u;
-    for (int g = g0; g < g1; ++g)
-        for (int q = g * 8; q < g * 8 + 8 && q < words; ++q) loc += __popc(s_bits[q]);
-    unsigned inc = loc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    unsigned run = inc - loc;
-    for (int q = 0; q < w; ++q) run += s_w[q];
-    for (int g = g0; g < g1; ++g) {
-        s_gp[g] = run;
-        for (int q = g * 8; q < g * 8 + 8 && q < words; ++q) run += __popc(s_bits[q]);
-    }
-    __syncthreads();
-    for (int i = t; i < n; i += 1024) {
-        const unsigned k = unit_key_bits(d, pk, i);
-        const int q = (int)(k >> 5);
-        unsigned r = s_gp[q >> 3] + __popc(s_bits[q] & ((1u << (k & 31)) - 1u));
-        for (int p = q & ~7; p < q; ++p) r += __popc(s_bits[p]);
-        sorted_ids[r] = (unsigned)i;
-    }
-}
-static bool g_unit_sort_radix = false;  // test hook otx_unit_sort_radix: force the radix path (parity of the two)
-
 // ------------------------------------------------------------------------------------ host helpers
 static IntegrateParams make_integrate_params(const ot_tsdf* vol, const float* depth, const uint8_t* color,
                                              const float* mult, const ot_intrinsics* in, const double* ext) {
@@ -1665,7 +1284,6 @@ static IntegrateParams make_integrate_params(const ot_tsdf* vol, const float* de
     return p;
 }
 
-struct BatchCtx;
 static ot_status launch_deferred(ot_tsdf* vol, hipStream_t stream, const BatchCtx* next);
 static ot_status ensure_mult(ot_tsdf* vol, const ot_intrinsics* in, hipStream_t stream) {
     if (vol->mult_valid && std::memcmp(&vol->mult_intr, in, sizeof(ot_intrinsics)) == 0) return OT_OK;
@@ -1706,19 +1324,13 @@ static ot_status check_frame(const ot_tsdf* vol, const void* depth, const uint8_
 constexpr int INT_GRID_MULT = 8;
 
 // the integrate instantiation of a batch: colour precision 64 (bit 1), reciprocal table (bit 0), fine slices (bit 2:
-// 2 voxels per lane along z, 32 waves per unit instead of 16 -- for batches with few units, below)
-static int g_int_fine = -1;  // test hook otx_integrate_fine: -1 by the batch's size (default), 0 coarse, 1 fine
-constexpr int DEFER_FINE_NUM = 21, DEFER_FINE_DEN = 8;  // units * 16 < 21/8 of the resident workgroups: 336 units
-static int g_fine_units = -1;  // its threshold form (deferred integrate: fine below this many units; -1 the default)
-static int g_stage_blocks = -1;  // test hook otx_touch_stage_blocks: staging-only touch workgroups (-1: 2 per tile)
+// 2 voxels per lane along z, 32 waves per unit instead of 16 -- for batches with few units, slice_form below);
 // bits 3-4 of a fine variant: the frame pipeline's depth KT - 1 (k_batch_integrate's ZB == 2 loop)
-static int g_int_depth = -1;  // test hook otx_integrate_depth: -1 the default (INT_FINE_KT), else KT in 1..3
 constexpr int INT_FINE_KT = 1;
 // Waves per workgroup of the coarse integrate: a finished wave frees its wave slot at once, but its
 // workgroup's place on the CU only when the slowest wave ends, so the smaller the workgroup the sooner the dispatcher
 // refills the slot.  The fine slices and the fused launches keep INT_WG waves.
 constexpr int INT_WG_DEFAULT = 1;
-static int g_int_wg = -1;  // test hook otx_integrate_workgroup: -1 the default rule (integrate_form), else 1, 2 or 4
 template <int WG>
 static const void* coarse_kernel(int variant) {
     static const void* const k[4] = {
@@ -1797,8 +1409,9 @@ static IntForm integrate_form(int variant, int rcp_hi) {
     f.wg = INT_WG;
     if (!(variant & 4)) {
         const int want = integrate_resident(variant, INT_WG, f.lds) * INT_WG;  // waves
-        f.wg = g_int_wg > 0 ? g_int_wg : INT_WG_DEFAULT;
-        while (g_int_wg <= 0 && f.wg < INT_WG && integrate_resident(variant, f.wg, f.lds) * f.wg < want) f.wg *= 2;
+        const int forced = g_tsdf_hooks.int_wg;  // otx_integrate_workgroup: 1, 2 or 4 at every table size
+        f.wg = forced > 0 ? forced : INT_WG_DEFAULT;
+        while (forced <= 0 && f.wg < INT_WG && integrate_resident(variant, f.wg, f.lds) * f.wg < want) f.wg *= 2;
     }
     f.fn = integrate_kernel(variant, f.wg);
     const int r = integrate_resident(variant, f.wg, f.lds);
@@ -1806,18 +1419,44 @@ static IntForm integrate_form(int variant, int rcp_hi) {
     return f;
 }
 
-// the context a batch's settle (and a replay) needs
-struct BatchCtx {
-    BatchTouchParams tp;
-    IntegrateParams ip0;
-    unsigned tiles;
-    int n, pc, variant, set;
-    bool defer = false;         // deferred integrate (k_integrate_touch / the next flush launches it)
-    bool split = false;         // split front end: a replay stages its units' tiles too (units the full hash dropped
-    StageMaskParams sq{};       // were in no work list of the first pass, so their footprints were never staged)
-    unsigned* smask = nullptr;  // the batch's tile masks (its parity)
-};
-static ot_status settle_batch(ot_tsdf* vol, const BatchCtx& bc, hipStream_t stream);
+// Coarse or fine slices for a batch of `est` units (est < 0: unknown, coarse), one rule with two thresholds:
+// Few units (a spatial shard, a small object): a (unit, quarter) item is a chain of the batch's frames, each frame
+// two dependent gather round trips plus ~270 dependent VALU instructions, so a batch too small to fill the GPU is
+// bound by that chain -- ~130 us per 64 frames whatever the unit count (tools/shard_scaling.py, r05g: rank 0 of
+// 16 / 32 / 64 shards 142 / 134 / 132 us).  Such batches take the fine slices (2 voxels per lane along z, twice
+// the items, the next frame's gathers issued beside this frame's colour gathers: 107 / 90 / 85 us; the same
+// per-voxel arithmetic, the same bits).
+// An integrate launched with its batch (Direct, Overlap): fine below 3/4 of the resident workgroups in (unit, quarter)
+// items -- with a quarter of the GPU's resident workgroups in items or more the coarse slices are as fast or faster
+// (1/8 shard 167 / 167 us, 1/4 242 / 280 us).  The estimate is the previous batch's count (direct_estimate).
+// A deferred integrate knows its batch's count (settle_batch read the mail of its units kernel): fine below 21/8 of
+// the resident workgroups, 336 units -- 8 sector ranks' batches of 135 / 161 / 317 units ran fine in 112 / 126 / 131 us
+// against 146 / 146 / 142 coarse, one of 367 units 167 against 148 (r06fn) -- or below otx_integrate_fine's unit count,
+// a threshold sweep that only the deferred launch reads; its fused kernels have one pipeline depth, INT_FINE_KT, the
+// launch with the batch also otx_integrate_depth's.
+constexpr int DIRECT_FINE_NUM = 3, DIRECT_FINE_DEN = 1;
+constexpr int DEFER_FINE_NUM = 21, DEFER_FINE_DEN = 8;
+static int slice_form(int variant, int64_t est, bool deferred) {
+    const TsdfHooks& h = g_tsdf_hooks;
+    const int64_t resident = integrate_grid(variant) / INT_GRID_MULT;
+    const int num = deferred ? DEFER_FINE_NUM : DIRECT_FINE_NUM, den = deferred ? DEFER_FINE_DEN : DIRECT_FINE_DEN;
+    const bool small = est >= 0 && est * INT_PARTS * 4 * den < resident * num;
+    const bool fine = h.int_fine > 0 || (deferred && h.fine_units >= 2 ? est >= 0 && est < h.fine_units
+                                                                       : h.int_fine < 0 && small);
+    if (!fine) return variant;
+    const int kt = !deferred && h.int_depth > 0 ? h.int_depth : INT_FINE_KT;
+    return variant | 4 | ((kt - 1) << 3);
+}
+// The unit count of a batch is known on the device only: the previous batch's (mailed) stands in for it, and a sharded
+// volume's first batch counts as small from 16 ranks on.
+// 2..15 ranks: coarse always.  A sector rank's batches swing between a few units and a full arc (r06e, rank 0
+// of 8: 135 / 677 / 662 / 317 units), so the previous batch mispredicts: the 677-unit batch took 214 us fine
+// against ~145 us coarse, and coarse-only steps were the faster (0.985 vs 1.053 ms, r06i)
+static int64_t direct_estimate(const ot_tsdf* vol) {
+    const int world = vol->dev.shard_world;
+    if (world > 1 && world < 16) return (int64_t)1 << 30;
+    return vol->last_batch_slots >= 0 ? vol->last_batch_slots : (world >= 16 ? 0 : (int64_t)1 << 30);
+}
 
 // auto (-1): on for sharded volumes (round 6, with their split front end: rank steps at 2 / 4 / 8 sector ranks 2.025 /
 // 1.383 / 1.024 ms with it against 2.117 / 1.416 / 1.050 without, r06h; 0.953 vs 0.985 at 8 with coarse slices, r06i),
@@ -1826,14 +1465,10 @@ static ot_status settle_batch(ot_tsdf* vol, const BatchCtx& bc, hipStream_t stre
 static bool overlap_on(const ot_tsdf* vol) {
     return vol->overlap_mode > 0 || (vol->overlap_mode < 0 && vol->dev.shard_world > 1);
 }
-static bool split_on(const ot_tsdf* vol);
-static bool tmask_fits(int w, int h);
-static bool defer_on(const ot_tsdf* vol, bool split);
 // the split front end: sharded volumes.  Its tile masks are written and read on the caller's stream only (mask kernel,
 // then staging), so one buffer serves the double-buffered front end too: the integrate on istream never reads them.
-static int g_split = -1;  // test hook otx_split_frontend: -1 by the volume (default), 0 never, 1 always (unsharded too)
 static bool split_on(const ot_tsdf* vol) {
-    const int mode = g_split >= 0 ? g_split : vol->split_mode;
+    const int mode = g_tsdf_hooks.split >= 0 ? g_tsdf_hooks.split : vol->split_mode;
     return mode > 0 || (mode < 0 && vol->dev.shard_world > 1);
 }
 // tile masks for w x h frames (each split batch's mask kernel writes its frames' maps whole)
@@ -1868,10 +1503,10 @@ static void* set_work(ot_tsdf* vol, int s) { return s == 0 ? vol->dev.work : vol
 // batch k + 1's touch (k_integrate_touch, one stream, no events) -- the default from 4 ranks on (r06k, sector rank steps:
 // 0.919 vs 1.003 ms at 8, 1.301 vs 1.336 at 4, but 2.165 vs 2.075 at 2, where the rank's integrate fills the GPU and the
 // double-buffered front end stays the default) unless the double-buffered front end is asked for (overlap mode 1)
-static int g_defer = -1;  // test hook otx_defer_integrate: -1 by the volume (default), 0 never, 1 with any split batch
 static bool defer_on(const ot_tsdf* vol, bool split) {
-    if (!split || g_defer == 0 || vol->overlap_mode > 0) return false;
-    return g_defer > 0 || vol->dev.shard_world >= 4;
+    const int hook = g_tsdf_hooks.defer;
+    if (!split || hook == 0 || vol->overlap_mode > 0) return false;
+    return hook > 0 || vol->dev.shard_world >= 4;
 }
 
 // order `stream` after the last batch's integrate when it ran on the volume's integrate stream
@@ -1896,276 +1531,6 @@ static ot_status ensure_overlap(ot_tsdf* vol) {
     }
     note_alloc();
     return OT_OK;
-}
-
-// Launch the deferred batch's integrate on `stream`: with the touch of batch `next` in one launch (k_integrate_touch), or
-// alone (next == nullptr: a flush).  Coarse slices, the variant's colour precision and division form.
-static ot_status launch_deferred(ot_tsdf* vol, hipStream_t stream, const BatchCtx* next) {
-    if (!vol->dfr_on) return OT_OK;
-    BatchCtx D;
-    std::memcpy(&D, vol->dfr_ctx, sizeof(BatchCtx));
-    vol->dfr_on = false;
-    if (stream != vol->dfr_stream) {  // the batch's front end ran on another stream
-        if (!vol->ev_dfr) OT_HIP_TRY(hipEventCreateWithFlags(&vol->ev_dfr, hipEventDisableTiming));
-        OT_HIP_TRY(hipEventRecord(vol->ev_dfr, vol->dfr_stream));
-        OT_HIP_TRY(hipStreamWaitEvent(stream, vol->ev_dfr, 0));
-    }
-    const BatchFrame* bf = vol->bset[D.set].bframes;
-    const UnitWork* uw = (const UnitWork*)set_work(vol, D.set);
-    const int* wc = vol->wcount + D.set;
-    // coarse, or fine slices for a batch of few units: its count is known here (settle_batch read the mail of its
-    // units kernel; the direct path guesses it from the previous batch), the rule of integrate_batch
-    int variant = D.variant & 3;
-    {
-        const int64_t units = vol->last_batch_slots;
-        const int resident = integrate_grid(variant) / INT_GRID_MULT;
-        // below DEFER_FINE_UNITS: 8 sector ranks' batches of 135 / 161 / 317 units ran fine in 112 / 126 / 131 us
-        // against 146 / 146 / 142 coarse, one of 367 units 167 against 148 (r06fn); a fraction of the resident
-        // workgroups, as the direct path's rule
-        const bool small = g_fine_units >= 2 ? units >= 0 && units < g_fine_units
-                                             : units >= 0 && units * INT_PARTS * 4 * DEFER_FINE_DEN <
-                                                                 (int64_t)resident * DEFER_FINE_NUM;
-        if (g_int_fine > 0 || ((g_int_fine < 0 || g_fine_units >= 2) && small))
-            variant |= 4 | ((INT_FINE_KT - 1) << 3);
-    }
-    const bool fine = (variant & 4) != 0;
-    const int nint = integrate_grid(variant);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (vol->profiling) {
-        OT_HIP_TRY(hipEventCreate(&e0));
-        OT_HIP_TRY(hipEventCreate(&e1));
-        OT_HIP_TRY(hipEventRecord(e0, stream));
-    }
-    if (next) {
-        const BatchFrame* tf = vol->bset[next->set].bframes;
-        BatchTouchParams tp = next->tp;
-        int tn = next->n;
-        int ni = nint;
-        void* args[] = {(void*)&bf, (void*)&D.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wc, (void*)&ni,
-                        (void*)&tf, (void*)&tp, (void*)&tn};
-        static const void* const kt[8] = {
-            (const void*)k_integrate_touch<false, false>,      (const void*)k_integrate_touch<false, true>,
-            (const void*)k_integrate_touch<true, false>,       (const void*)k_integrate_touch<true, true>,
-            (const void*)k_integrate_touch_fine<false, false>, (const void*)k_integrate_touch_fine<false, true>,
-            (const void*)k_integrate_touch_fine<true, false>,  (const void*)k_integrate_touch_fine<true, true>};
-        const unsigned grid = (unsigned)nint + next->tiles * (unsigned)((tn + tp.tf - 1) / tp.tf);
-        OT_HIP_TRY(hipLaunchKernel(kt[(variant & 3) + (fine ? 4 : 0)], dim3(grid), dim3(64 * INT_WG), args, 0, stream));
-    } else {
-        void* args[] = {(void*)&bf, (void*)&D.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wc};
-        const IntForm f = integrate_form(variant, D.ip0.rcp_hi);
-        OT_HIP_TRY(hipLaunchKernel(f.fn, dim3(f.grid), dim3(64 * f.wg), args, f.lds, stream));
-    }
-    OT_LAUNCH_CHECK();
-    if (vol->profiling) {
-        OT_HIP_TRY(hipEventRecord(e1, stream));
-        vol->prof_events.emplace_back(e0, e1);
-    }
-    return OT_OK;
-}
-
-static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n, hipStream_t stream) {
-    const ot_intrinsics& in = frames[0].intr;
-    ot_status st = wait_normals(vol, stream);  // deferred vertex normals of the last mesh still read the volume
-    if (st != OT_OK) return st;
-    st = ensure_mult(vol, &in, stream);
-    if (st != OT_OK) return st;
-    const bool split = split_on(vol) && tmask_fits(in.width, in.height);
-    const bool defer = defer_on(vol, split);
-    const bool ovl = !defer && overlap_on(vol);
-    if ((ovl || defer) && (st = ensure_overlap(vol)) != OT_OK) return st;
-    const int set = (ovl || defer) ? vol->bset_next : 0;
-    if (ovl || defer) vol->bset_next ^= 1;
-    auto& bs = vol->bset[set];
-    // (deferred: the set's last batch was integrated inside the launch with the previous batch's touch, queued on
-    // this stream before that batch's units kernel -- done before anything below restages the set)
-    // the set's previous batch (two batches ago) must have finished its integrate before its buffers are restaged
-    // (an event never recorded counts as complete)
-    if (ovl) OT_HIP_TRY(hipStreamWaitEvent(stream, bs.ev_done, 0));
-    const int64_t npx = (int64_t)in.width * in.height;
-    if (bs.cap < npx * n) {
-        if (bs.bdc) {
-            OT_HIP_TRY(hipStreamSynchronize(stream));
-            if (vol->istream) OT_HIP_TRY(hipStreamSynchronize(vol->istream));
-            OT_HIP_TRY(hipFree(bs.bdc));
-            bs.bdc = nullptr;
-        }
-        const int64_t cap = npx * std::max(n, std::min(vol->batch_max, MAX_BATCH));
-        OT_HIP_TRY(hipMalloc(&bs.bdc, sizeof(uint2) * cap));
-        bs.cap = cap;
-    }
-    // per-frame parameters: pinned host staging (double-buffered, event-guarded) -> device
-    const int hb = vol->hb_next;  // (the last batch from this half was copied: settle_batch saw its units kernel mail)
-    vol->hb_next ^= 1;
-    BatchFrame* host = vol->hbframes + hb * MAX_BATCH;
-    BatchCtx bc;
-    bc.ip0 = make_integrate_params(vol, nullptr, nullptr, vol->mult, &in, frames[0].extrinsic);
-    for (int k = 0; k < n; ++k) {
-        const PendingFrame& f = frames[k];
-        BatchFrame& b = host[k];
-        b.depth16 = f.depth;
-        b.depthf = f.depth ? nullptr : f.depthf;
-        b.color = (vol->color_type == OT_COLOR_RGB8) ? f.color : nullptr;
-        b.dc = bs.bdc + npx * k;
-        b.pad = 0;
-        double pose[16];
-        inverse4(f.extrinsic, pose);
-        for (int i = 0; i < 12; ++i) b.pose[i] = pose[i];
-        float E[16];
-        for (int i = 0; i < 16; ++i) E[i] = (float)f.extrinsic[i];
-        for (int i = 0; i < 12; ++i) b.E[i] = E[i];
-        b.es[0] = E[0 * 4 + 2] * bc.ip0.vl;
-        b.es[1] = E[1 * 4 + 2] * bc.ip0.vl;
-        b.es[2] = E[2 * 4 + 2] * bc.ip0.vl;
-        b.scale = (float)f.depth_scale;
-        b.trunc = f.depth_trunc;
-    }
-    hipLaunchKernelGGL(k_copy_frames, dim3(1), dim3(COPY_FRAMES_LANES), 0, stream, (const uint4*)host,
-                       (uint4*)bs.bframes, (int)(sizeof(BatchFrame) / 16) * n);
-    // this batch's pair counter: zeroed by reset, or by the previous batch's k_batch_units (no memset here)
-    const int pc = vol->batch_pc;
-    BatchTouchParams& tp = bc.tp;
-    tp.npx = npx;
-    tp.pc = pc;
-    tp.W = in.width;
-    tp.stride = vol->stride;
-    tp.ws = (in.width + vol->stride - 1) / vol->stride;
-    tp.hs = (in.height + vol->stride - 1) / vol->stride;
-    tp.fx = in.fx;
-    tp.fy = in.fy;
-    tp.cx = in.cx;
-    tp.cy = in.cy;
-    tp.trunc = vol->sdf_trunc;
-    tp.unit_len = vol->unit_length;
-    tp.inv_unit = 1.0 / vol->unit_length;
-    tp.slot_cap = (int)vol->hash_cap;
-    bc.tiles = (unsigned)(((tp.ws + TT - 1) / TT) * ((tp.hs + TT - 1) / TT));
-    tp.tiles = (int)bc.tiles;
-    tp.stage_blocks = g_stage_blocks < 0 ? 2 * (int)bc.tiles : g_stage_blocks;
-    tp.tf = g_touch_tf;
-    // sharded volume: split front end (touch without staging -> units -> tile mask -> staging of the marked tiles)
-    tp.sample_stage = split ? 1 : 0;
-    if (split) {
-        tp.stage_blocks = -1;
-        if ((st = ensure_tmask(vol, in.width, in.height, stream)) != OT_OK) return st;
-    }
-    bc.n = n;
-    bc.pc = pc;
-    bc.set = set;
-    bc.defer = defer;
-    hipEvent_t f0 = nullptr, f1 = nullptr;  // front end (staging + touch + units): the part a sharded volume repeats
-    if (vol->profiling) {
-        OT_HIP_TRY(hipEventCreate(&f0));
-        OT_HIP_TRY(hipEventCreate(&f1));
-        OT_HIP_TRY(hipEventRecord(f0, stream));
-    }
-    UnitWork* work = (UnitWork*)set_work(vol, set);
-    int* wcount = (ovl || defer) ? vol->wcount + set : vol->dev.counters + pc;
-    if (defer && vol->dfr_on) {  // the last batch's integrate and this batch's touch in one launch
-        if ((st = launch_deferred(vol, stream, &bc)) != OT_OK) return st;
-    } else if (split) {
-        hipLaunchKernelGGL(k_batch_touch_split, dim3(bc.tiles, (unsigned)((n + tp.tf - 1) / tp.tf)), dim3(256), 0,
-                           stream, (const BatchFrame*)bs.bframes, tp, vol->dev, n);
-    } else {
-        hipLaunchKernelGGL(k_batch_touch<false>,
-                           dim3(bc.tiles + (unsigned)std::max(0, tp.stage_blocks), (unsigned)((n + tp.tf - 1) / tp.tf)),
-                           dim3(256), 0, stream, (const BatchFrame*)bs.bframes, tp, vol->dev, n);
-    }
-    hipLaunchKernelGGL(k_batch_units<false>, dim3(256), dim3(256), 0, stream, vol->dev, work, pc,
-                       vol->hmail + OT_MAIL_WORDS, (ovl || defer) ? wcount : (int*)nullptr, ++vol->units_seq);
-    if (split) {
-        StageMaskParams q;
-        q.W = in.width;
-        q.H = in.height;
-        q.tiles_x = (in.width + STX - 1) / STX;
-        q.tiles_y = (in.height + STY - 1) / STY;
-        q.wpr = (q.tiles_x + 31) / 32;
-        q.fx = bc.ip0.fx, q.fy = bc.ip0.fy, q.cx = bc.ip0.cx, q.cy = bc.ip0.cy;
-        q.vl = bc.ip0.vl, q.half = bc.ip0.half;
-        q.unit_len = vol->unit_length;
-        q.nframes = n;
-        bc.split = true;
-        bc.sq = q;
-        bc.smask = vol->tmask;
-        launch_stage((const BatchFrame*)bs.bframes, q, (const UnitWork*)work, (const int*)wcount, vol->tmask, stream);
-    }
-    // reciprocal-table kernel while every weight + 1 is an integer <= RCP_N: weights count updates, at most one
-    // per frame since reset, unless units were imported (k_batch_integrate: Markstein's exact correction)
-    const bool fast = !vol->imported && (int64_t)vol->frame_id + n < RCP_N;
-    bc.variant = (vol->color64 ? 2 : 0) + (fast ? 1 : 0);
-    // the table entries the batch can read: a weight is at most the frames since reset, so weight + 1 <= frame_id + n
-    // (before frame_id advances; kept in the batch's context for a deferred launch or a replay)
-    bc.ip0.rcp_hi = (int)std::min<int64_t>((int64_t)vol->frame_id + n, RCP_N);
-    // Few units (a spatial shard, a small object): a (unit, quarter) item is a chain of the batch's frames, each frame
-    // two dependent gather round trips plus ~270 dependent VALU instructions, so a batch too small to fill the GPU is
-    // bound by that chain -- ~130 us per 64 frames whatever the unit count (tools/shard_scaling.py, r05g: rank 0 of
-    // 16 / 32 / 64 shards 142 / 134 / 132 us).  Such batches take the fine slices (2 voxels per lane along z, twice
-    // the items, the next frame's gathers issued beside this frame's colour gathers: 107 / 90 / 85 us; the same
-    // per-voxel arithmetic, the same bits).  With a quarter of the GPU's resident workgroups in items or more the
-    // coarse slices are as fast or faster (1/8 shard 167 / 167 us, 1/4 242 / 280 us).  The unit count of a batch is
-    // known on the device only: the previous batch's (mailed) stands in for it, and a sharded volume's first batch
-    // counts as small from 16 ranks on.
-    {
-        const int resident = integrate_grid(bc.variant) / INT_GRID_MULT;
-        // 2..15 ranks: coarse always.  A sector rank's batches swing between a few units and a full arc (r06e, rank 0
-        // of 8: 135 / 677 / 662 / 317 units), so the previous batch mispredicts: the 677-unit batch took 214 us fine
-        // against ~145 us coarse, and coarse-only steps were the faster (0.985 vs 1.053 ms, r06i)
-        const int64_t est = vol->dev.shard_world > 1 && vol->dev.shard_world < 16 ? (int64_t)1 << 30
-                            : vol->last_batch_slots >= 0 ? vol->last_batch_slots
-                                                         : (vol->dev.shard_world >= 16 ? 0 : (int64_t)1 << 30);
-        const bool fine = !defer && (g_int_fine > 0 || (g_int_fine < 0 && est * INT_PARTS * 4 < (int64_t)resident * 3));
-        if (fine) bc.variant |= 4 | (((g_int_depth > 0 ? g_int_depth : INT_FINE_KT) - 1) << 3);
-    }
-    if (defer) {  // the integrate waits for the next batch's touch (or the next flush)
-        if (vol->profiling) {
-            OT_HIP_TRY(hipEventRecord(f1, stream));
-            vol->prof_fe_events.emplace_back(f0, f1);
-        }
-        static_assert(sizeof(BatchCtx) <= sizeof(vol->dfr_ctx), "deferred batch context");
-        std::memcpy(vol->dfr_ctx, &bc, sizeof(BatchCtx));
-        vol->dfr_on = true;
-        vol->dfr_stream = stream;
-        vol->batch_pc ^= 1;
-        vol->frame_id += n;
-        vol->sorted_frame = -1;
-        vol->early_frame = vol->frame_id;
-        return settle_batch(vol, bc, stream);
-    }
-    const IntForm form = integrate_form(bc.variant, bc.ip0.rcp_hi);
-    // overlap: the integrate on istream behind this set's units kernel (and the previous batch's integrate: same
-    // stream), so the caller's stream is free for the next batch's front end
-    hipStream_t is = stream;
-    if (ovl) {
-        OT_HIP_TRY(hipEventRecord(bs.ev_units, stream));
-        OT_HIP_TRY(hipStreamWaitEvent(vol->istream, bs.ev_units, 0));
-        is = vol->istream;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (vol->profiling) {
-        OT_HIP_TRY(hipEventRecord(f1, stream));
-        vol->prof_fe_events.emplace_back(f0, f1);
-        OT_HIP_TRY(hipEventCreate(&e0));
-        OT_HIP_TRY(hipEventCreate(&e1));
-        OT_HIP_TRY(hipEventRecord(e0, is));
-    }
-    const BatchFrame* bf = bs.bframes;
-    const UnitWork* uw = work;
-    const int* wc = wcount;
-    void* args[] = {(void*)&bf, (void*)&bc.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wc};
-    OT_HIP_TRY(hipLaunchKernel(form.fn, dim3(form.grid), dim3(64 * form.wg), args, form.lds, is));
-    vol->batch_pc ^= 1;  // only once this batch's kernels are queued (its units kernel zeroes the other counter)
-    OT_LAUNCH_CHECK();
-    if (vol->profiling) {
-        OT_HIP_TRY(hipEventRecord(e1, is));
-        vol->prof_events.emplace_back(e0, e1);
-    }
-    if (ovl) {
-        OT_HIP_TRY(hipEventRecord(bs.ev_done, is));
-        vol->last_set = set;
-    }
-    vol->frame_id += n;
-    vol->sorted_frame = -1;
-    vol->early_frame = vol->frame_id;  // the mailed counters are final for this frame count (see units_seq)
-    return settle_batch(vol, bc, stream);
 }
 
 // ------------------------------------------------------------------------------------------ unbounded unit pool
@@ -2249,6 +1614,182 @@ static ot_status grow_pool(ot_tsdf* vol, int64_t need, int n_used, hipStream_t s
     return OT_OK;
 }
 
+// ------------------------------------------------------------------------------------------ the batch pipeline
+// integrate_batch: plan_batch chooses how the batch runs, once; the launchers below are each written once and read the
+// plan (through the batch's context); settle_batch replays with the same launchers after pool growth.
+
+// How a batch of frames with intrinsics `in` and pair counter `pc` runs: the mode, the split front end, the batch's set
+// and where its work list's length lives.  Nothing after this asks the volume or the hooks for the mode again.
+static ot_status plan_batch(ot_tsdf* vol, const ot_intrinsics& in, int pc, BatchPlan& p) {
+    p.split = split_on(vol) && tmask_fits(in.width, in.height);
+    p.mode = defer_on(vol, p.split) ? BatchMode::Deferred : overlap_on(vol) ? BatchMode::Overlap : BatchMode::Direct;
+    p.wcount = vol->dev.counters + pc;
+    if (p.mode != BatchMode::Direct) {  // the sets alternate; each has its own copy of the count
+        ot_status st = ensure_overlap(vol);
+        if (st != OT_OK) return st;
+        p.set = vol->bset_next;
+        vol->bset_next ^= 1;
+        p.wcount = p.wcopy = vol->wcount + p.set;
+    }
+    return OT_OK;
+}
+
+// per-frame parameters of a batch into its pinned staging half; frame k's staged records at bdc + npx * k
+static void fill_batch_frames(const ot_tsdf* vol, const PendingFrame* frames, int n, uint2* bdc, int64_t npx, float vl,
+                              BatchFrame* host) {
+    for (int k = 0; k < n; ++k) {
+        const PendingFrame& f = frames[k];
+        BatchFrame& b = host[k];
+        b.depth16 = f.depth;
+        b.depthf = f.depth ? nullptr : f.depthf;
+        b.color = (vol->color_type == OT_COLOR_RGB8) ? f.color : nullptr;
+        b.dc = bdc + npx * k;
+        b.pad = 0;
+        double pose[16];
+        inverse4(f.extrinsic, pose);
+        for (int i = 0; i < 12; ++i) b.pose[i] = pose[i];
+        float E[12];  // (the pinned staging is only written)
+        for (int i = 0; i < 12; ++i) b.E[i] = E[i] = (float)f.extrinsic[i];
+        for (int i = 0; i < 3; ++i) b.es[i] = E[i * 4 + 2] * vl;
+        b.scale = (float)f.depth_scale;
+        b.trunc = f.depth_trunc;
+    }
+}
+
+static BatchTouchParams make_touch_params(const ot_tsdf* vol, const ot_intrinsics& in, int pc, bool split) {
+    BatchTouchParams tp;
+    tp.npx = (int64_t)in.width * in.height;
+    tp.pc = pc;
+    tp.W = in.width, tp.stride = vol->stride;
+    tp.ws = (in.width + vol->stride - 1) / vol->stride;
+    tp.hs = (in.height + vol->stride - 1) / vol->stride;
+    tp.fx = in.fx, tp.fy = in.fy, tp.cx = in.cx, tp.cy = in.cy;
+    tp.trunc = vol->sdf_trunc;
+    tp.unit_len = vol->unit_length, tp.inv_unit = 1.0 / vol->unit_length;
+    tp.slot_cap = (int)vol->hash_cap;
+    tp.tiles = ((tp.ws + TT - 1) / TT) * ((tp.hs + TT - 1) / TT);
+    tp.stage_blocks = g_tsdf_hooks.stage_blocks < 0 ? 2 * tp.tiles : g_tsdf_hooks.stage_blocks;
+    tp.tf = g_tsdf_hooks.touch_tf > 0 ? g_tsdf_hooks.touch_tf : TF;
+    // sharded volume: split front end (touch without staging -> units -> tile mask -> staging of the marked tiles)
+    tp.sample_stage = split ? 1 : 0;
+    if (split) tp.stage_blocks = -1;
+    return tp;
+}
+
+static StageMaskParams make_stage_params(const ot_tsdf* vol, const ot_intrinsics& in, const IntegrateParams& ip, int n) {
+    StageMaskParams q;
+    q.W = in.width, q.H = in.height;
+    q.tiles_x = (in.width + STX - 1) / STX;
+    q.tiles_y = (in.height + STY - 1) / STY;
+    q.wpr = (q.tiles_x + 31) / 32;
+    q.fx = ip.fx, q.fy = ip.fy, q.cx = ip.cx, q.cy = ip.cy;
+    q.vl = ip.vl, q.half = ip.half;
+    q.unit_len = vol->unit_length;
+    q.nframes = n;
+    return q;
+}
+
+// a profiling event pair around work on a stream (ot_tsdf_set_profiling; nothing when it is off)
+struct ProfPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+static ot_status prof_open(const ot_tsdf* vol, ProfPair& p, hipStream_t stream) {
+    if (!vol->profiling) return OT_OK;
+    OT_HIP_TRY(hipEventCreate(&p.e0));
+    OT_HIP_TRY(hipEventCreate(&p.e1));
+    OT_HIP_TRY(hipEventRecord(p.e0, stream));
+    return OT_OK;
+}
+static ot_status prof_close(const ProfPair& p, hipStream_t stream, decltype(ot_tsdf::prof_events)& list) {
+    if (!p.e0) return OT_OK;
+    OT_HIP_TRY(hipEventRecord(p.e1, stream));
+    list.emplace_back(p.e0, p.e1);
+    return OT_OK;
+}
+
+// A batch's front end on `stream`: touch -> units (-> tile mask -> staging of the marked tiles when split).
+// First pass (replay false; touch false: a fused launch has run the batch's touch already), or the replay after pool
+// growth: touch again from the staged depths, then list the units the batch's integrate skipped (those without an id),
+// counted in the batch's own pair counter -- or, Deferred, the whole list again into the set's count (nothing of the
+// batch is integrated yet, and it stays deferred).
+static void launch_front_end(ot_tsdf* vol, const BatchCtx& bc, bool replay, bool touch, hipStream_t stream) {
+    const BatchPlan& plan = bc.plan;
+    const BatchFrame* bf = vol->bset[plan.set].bframes;
+    UnitWork* work = (UnitWork*)set_work(vol, plan.set);
+    BatchTouchParams tp = bc.tp;
+    tp.slot_cap = (int)vol->hash_cap;  // (a replay's hash has grown)
+    if (touch) {  // the staging-only workgroups (stage_blocks > 0) belong to the first pass of an unsplit batch
+        const auto touch_k = replay ? k_batch_touch<true> : plan.split ? k_batch_touch_split : k_batch_touch<false>;
+        const unsigned tiles = (unsigned)tp.tiles + (replay ? 0u : (unsigned)std::max(0, tp.stage_blocks));
+        hipLaunchKernelGGL(touch_k, dim3(tiles, (unsigned)((bc.n + tp.tf - 1) / tp.tf)), dim3(256), 0, stream, bf, tp,
+                           vol->dev, bc.n);
+    }
+    const bool missing_only = replay && plan.mode != BatchMode::Deferred;
+    int* wcopy = missing_only ? nullptr : plan.wcopy;
+    const auto units_k = missing_only ? k_batch_units<true> : k_batch_units<false>;
+    hipLaunchKernelGGL(units_k, dim3(256), dim3(256), 0, stream, vol->dev, work, bc.pc, vol->hmail + OT_MAIL_WORDS, wcopy,
+                       ++vol->units_seq);
+    if (plan.split)  // (a replay: from the caller's frames, valid until this flush returns)
+        launch_stage(bf, bc.sq, (const UnitWork*)work, (const int*)(wcopy ? wcopy : vol->dev.counters + bc.pc), bc.smask,
+                     stream);
+}
+
+// k_batch_integrate over batch `bc`'s work list (`wcount` entries) on `stream`, in the form `variant`
+static ot_status launch_integrate(ot_tsdf* vol, const BatchCtx& bc, int variant, const int* wcount, hipStream_t stream) {
+    const BatchFrame* bf = vol->bset[bc.plan.set].bframes;
+    const UnitWork* uw = (const UnitWork*)set_work(vol, bc.plan.set);
+    void* args[] = {(void*)&bf, (void*)&bc.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wcount};
+    const IntForm f = integrate_form(variant, bc.ip0.rcp_hi);
+    OT_HIP_TRY(hipLaunchKernel(f.fn, dim3(f.grid), dim3(64 * f.wg), args, f.lds, stream));
+    OT_LAUNCH_CHECK();
+    return OT_OK;
+}
+
+// order `stream` after the deferred batch's front end (and all before it) when that ran on another stream
+static ot_status follow_deferred(ot_tsdf* vol, hipStream_t stream) {
+    if (stream == vol->dfr_stream) return OT_OK;
+    if (!vol->ev_dfr) OT_HIP_TRY(hipEventCreateWithFlags(&vol->ev_dfr, hipEventDisableTiming));
+    OT_HIP_TRY(hipEventRecord(vol->ev_dfr, vol->dfr_stream));
+    OT_HIP_TRY(hipStreamWaitEvent(stream, vol->ev_dfr, 0));
+    vol->dfr_stream = stream;
+    return OT_OK;
+}
+
+// Launch the deferred batch's integrate on `stream`: with the touch of batch `next` in one launch (k_integrate_touch), or
+// alone (next == nullptr: a flush, or a next batch that does not fuse).  The variant's colour precision and division
+// form; its slices by the batch's unit count, known here (slice_form).
+static ot_status launch_deferred(ot_tsdf* vol, hipStream_t stream, const BatchCtx* next) {
+    if (!vol->dfr_on) return OT_OK;
+    ot_status st = follow_deferred(vol, stream);
+    if (st != OT_OK) return st;
+    vol->dfr_on = false;
+    const BatchCtx& D = vol->dfr;
+    const int variant = slice_form(D.variant & 3, vol->last_batch_slots, true);
+    ProfPair timed;
+    if ((st = prof_open(vol, timed, stream)) != OT_OK) return st;
+    if (next) {
+        const BatchFrame* bf = vol->bset[D.plan.set].bframes;
+        const UnitWork* uw = (const UnitWork*)set_work(vol, D.plan.set);
+        const int* wc = D.plan.wcount;
+        const BatchFrame* tf = vol->bset[next->plan.set].bframes;
+        const BatchTouchParams& tp = next->tp;
+        const int tn = next->n, ni = integrate_grid(variant);
+        void* args[] = {(void*)&bf, (void*)&D.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wc, (void*)&ni,
+                        (void*)&tf, (void*)&tp, (void*)&tn};
+        static const void* const kt[8] = {
+            (const void*)k_integrate_touch<false, false>,      (const void*)k_integrate_touch<false, true>,
+            (const void*)k_integrate_touch<true, false>,       (const void*)k_integrate_touch<true, true>,
+            (const void*)k_integrate_touch_fine<false, false>, (const void*)k_integrate_touch_fine<false, true>,
+            (const void*)k_integrate_touch_fine<true, false>,  (const void*)k_integrate_touch_fine<true, true>};
+        const unsigned grid = (unsigned)ni + (unsigned)tp.tiles * (unsigned)((tn + tp.tf - 1) / tp.tf);
+        OT_HIP_TRY(hipLaunchKernel(kt[variant & 7], dim3(grid), dim3(64 * INT_WG), args, 0, stream));
+        OT_LAUNCH_CHECK();
+    } else if ((st = launch_integrate(vol, D, variant, D.plan.wcount, stream)) != OT_OK) {
+        return st;
+    }
+    return prof_close(timed, stream, vol->prof_events);
+}
+
 // After each batch: the counters its units kernel mailed (mail_wait on units_seq: the host waits for the units kernel,
 // not for the integrate queued behind it, so the GPU keeps its queue).  Units the pool could not hold (C_OVERFLOW), or keys the
 // hash could not hold (C_HASHERR bit 0), were skipped by the batch's integrate: grow, then replay the batch for exactly
@@ -2289,37 +1830,114 @@ static ot_status settle_batch(ot_tsdf* vol, const BatchCtx& bc, hipStream_t stre
         h[bc.pc] = 0;  // the replay's touched-slot count (the batch's own pair counter; the next batch's stays zero)
         OT_HIP_TRY(hipMemcpy(vol->dev.counters, h, sizeof(h), hipMemcpyHostToDevice));
         // the replay, all on the caller's stream, from the batch's set (its staging is intact: nothing restaged it)
-        BatchTouchParams tp = bc.tp;
-        tp.slot_cap = (int)vol->hash_cap;
-        const BatchFrame* bf = vol->bset[bc.set].bframes;
-        UnitWork* work = (UnitWork*)set_work(vol, bc.set);
-        hipLaunchKernelGGL(k_batch_touch<true>, dim3(bc.tiles, (unsigned)((bc.n + tp.tf - 1) / tp.tf)), dim3(256), 0, stream,
-                           bf, tp, vol->dev, bc.n);
-        if (bc.defer) {  // nothing of the batch is integrated yet: rebuild its whole work list, restage, stay deferred
-            hipLaunchKernelGGL(k_batch_units<false>, dim3(256), dim3(256), 0, stream, vol->dev, work, bc.pc,
-                               vol->hmail + OT_MAIL_WORDS, vol->wcount + bc.set, ++vol->units_seq);
-            launch_stage(bf, bc.sq, (const UnitWork*)work, (const int*)(vol->wcount + bc.set), bc.smask, stream);
+        launch_front_end(vol, bc, true, true, stream);
+        if (bc.plan.mode == BatchMode::Deferred) {  // the whole work list is rebuilt; the batch stays deferred
             OT_LAUNCH_CHECK();
             continue;
         }
-        hipLaunchKernelGGL(k_batch_units<true>, dim3(256), dim3(256), 0, stream, vol->dev, work, bc.pc,
-                           vol->hmail + OT_MAIL_WORDS, (int*)nullptr, ++vol->units_seq);
-        if (bc.split) {  // the replayed units' tiles, from the caller's frames (valid until this flush returns)
-            launch_stage(bf, bc.sq, (const UnitWork*)work, (const int*)(vol->dev.counters + bc.pc), bc.smask, stream);
-        }
-        const UnitWork* uw = work;
-        const int* wc = vol->dev.counters + bc.pc;
-        void* args[] = {(void*)&bf, (void*)&bc.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wc};
-        const IntForm f = integrate_form(bc.variant, bc.ip0.rcp_hi);
-        OT_HIP_TRY(hipLaunchKernel(f.fn, dim3(f.grid), dim3(64 * f.wg), args, f.lds, stream));
-        OT_LAUNCH_CHECK();
+        st = launch_integrate(vol, bc, bc.variant, vol->dev.counters + bc.pc, stream);
+        if (st != OT_OK) return st;
         vol->last_set = -1;  // the replay ran on the caller's stream, after both streams drained
         vol->sorted_frame = -1;
     }
 }
 
+static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n, hipStream_t stream) {
+    const ot_intrinsics& in = frames[0].intr;
+    ot_status st = wait_normals(vol, stream);  // deferred vertex normals of the last mesh still read the volume
+    if (st != OT_OK || (st = ensure_mult(vol, &in, stream)) != OT_OK) return st;
+    BatchCtx bc;
+    // this batch's pair counter: zeroed by reset, or by the previous batch's k_batch_units (no memset here)
+    bc.pc = vol->batch_pc;
+    bc.n = n;
+    if ((st = plan_batch(vol, in, bc.pc, bc.plan)) != OT_OK) return st;
+    const BatchPlan& plan = bc.plan;
+    // A pending deferred batch is handed over here, before anything below restages a set.  On another stream than its
+    // front end's, this stream first waits for that one: this batch's set was last integrated there, inside the launch
+    // with the deferred batch's touch (queued before its units kernel).  And a batch that does not fuse with it (the mode changed: the hooks, the overlap
+    // setting, an image size the tile masks do not fit) launches it alone first -- else it would stay pending while its
+    // set is restaged.  On one stream with a constant mode neither issues a call.
+    if (vol->dfr_on) {
+        if ((st = follow_deferred(vol, stream)) != OT_OK) return st;
+        if (plan.mode != BatchMode::Deferred && (st = launch_deferred(vol, stream, nullptr)) != OT_OK) return st;
+    }
+    auto& bs = vol->bset[plan.set];
+    // Overlap: the set's previous batch (two batches ago) must have finished its integrate before its buffers are
+    // restaged (an event never recorded counts as complete)
+    if (plan.mode == BatchMode::Overlap) OT_HIP_TRY(hipStreamWaitEvent(stream, bs.ev_done, 0));
+    const int64_t npx = (int64_t)in.width * in.height;
+    if (bs.cap < npx * n) {
+        if (bs.bdc) {
+            OT_HIP_TRY(hipStreamSynchronize(stream));
+            if (vol->istream) OT_HIP_TRY(hipStreamSynchronize(vol->istream));
+            OT_HIP_TRY(hipFree(bs.bdc));
+            bs.bdc = nullptr;
+        }
+        const int64_t cap = npx * std::max(n, std::min(vol->batch_max, MAX_BATCH));
+        OT_HIP_TRY(hipMalloc(&bs.bdc, sizeof(uint2) * cap));
+        bs.cap = cap;
+    }
+    // per-frame parameters: pinned host staging (double-buffered) -> device
+    BatchFrame* host = vol->hbframes + vol->hb_next * MAX_BATCH;  // (the last batch from this half was copied:
+    vol->hb_next ^= 1;                                            // settle_batch saw its units kernel mail)
+    bc.ip0 = make_integrate_params(vol, nullptr, nullptr, vol->mult, &in, frames[0].extrinsic);
+    fill_batch_frames(vol, frames, n, bs.bdc, npx, bc.ip0.vl, host);
+    hipLaunchKernelGGL(k_copy_frames, dim3(1), dim3(COPY_FRAMES_LANES), 0, stream, (const uint4*)host,
+                       (uint4*)bs.bframes, (int)(sizeof(BatchFrame) / 16) * n);
+    bc.tp = make_touch_params(vol, in, bc.pc, plan.split);
+    if (plan.split) {
+        if ((st = ensure_tmask(vol, in.width, in.height, stream)) != OT_OK) return st;
+        bc.sq = make_stage_params(vol, in, bc.ip0, n);
+        bc.smask = vol->tmask;
+    }
+    // reciprocal-table kernel while every weight + 1 is an integer <= RCP_N: weights count updates, at most one
+    // per frame since reset, unless units were imported (k_batch_integrate: Markstein's exact correction)
+    const bool fast = !vol->imported && (int64_t)vol->frame_id + n < RCP_N;
+    bc.variant = (vol->color64 ? 2 : 0) + (fast ? 1 : 0);
+    // the table entries the batch can read: a weight is at most the frames since reset, so weight + 1 <= frame_id + n
+    // (before frame_id advances; kept in the batch's context for a deferred launch or a replay)
+    bc.ip0.rcp_hi = (int)std::min<int64_t>((int64_t)vol->frame_id + n, RCP_N);
+    // (a deferred integrate takes its slices when it is launched, by its own unit count)
+    if (plan.mode != BatchMode::Deferred) bc.variant = slice_form(bc.variant, direct_estimate(vol), false);
+
+    ProfPair fe;  // front end (staging + touch + units): the part a sharded volume repeats
+    if ((st = prof_open(vol, fe, stream)) != OT_OK) return st;
+    // Deferred: the last batch's integrate and this batch's touch in one launch
+    const bool fused = plan.mode == BatchMode::Deferred && vol->dfr_on;
+    if (fused && (st = launch_deferred(vol, stream, &bc)) != OT_OK) return st;
+    launch_front_end(vol, bc, false, !fused, stream);
+    if (plan.mode == BatchMode::Deferred) {  // the integrate waits for the next batch's touch (or the next flush)
+        if ((st = prof_close(fe, stream, vol->prof_fe_events)) != OT_OK) return st;
+        vol->dfr = bc;
+        vol->dfr_on = true, vol->dfr_stream = stream;
+    } else {
+        // Overlap: the integrate on istream behind this set's units kernel (and the previous batch's integrate: same
+        // stream), so the caller's stream is free for the next batch's front end
+        hipStream_t is = stream;
+        if (plan.mode == BatchMode::Overlap) {
+            OT_HIP_TRY(hipEventRecord(bs.ev_units, stream));
+            OT_HIP_TRY(hipStreamWaitEvent(vol->istream, bs.ev_units, 0));
+            is = vol->istream;
+        }
+        if ((st = prof_close(fe, stream, vol->prof_fe_events)) != OT_OK) return st;
+        ProfPair timed;
+        if ((st = prof_open(vol, timed, is)) != OT_OK) return st;
+        if ((st = launch_integrate(vol, bc, bc.variant, plan.wcount, is)) != OT_OK) return st;
+        if ((st = prof_close(timed, is, vol->prof_events)) != OT_OK) return st;
+        if (plan.mode == BatchMode::Overlap) {
+            OT_HIP_TRY(hipEventRecord(bs.ev_done, is));
+            vol->last_set = plan.set;
+        }
+    }
+    vol->batch_pc ^= 1;  // only once this batch's kernels are queued (its units kernel zeroes the other counter)
+    vol->frame_id += n;
+    vol->sorted_frame = -1;
+    vol->early_frame = vol->frame_id;  // the mailed counters are final for this frame count (see units_seq)
+    return settle_batch(vol, bc, stream);
+}
+
 // room for `extra` more units before a kernel that allocates up to that many (imports): grow now if needed
-static ot_status reserve_units(ot_tsdf* vol, int64_t extra, hipStream_t stream) {
+ot_status reserve_units(ot_tsdf* vol, int64_t extra, hipStream_t stream) {
     int nu = 0;
     OT_HIP_TRY(hipMemcpyAsync(&nu, vol->dev.counters + C_UNITS, sizeof(int), hipMemcpyDeviceToHost, stream));
     OT_HIP_TRY(hipStreamSynchronize(stream));
@@ -2363,302 +1981,11 @@ ot_status tsdf_flush(ot_tsdf* vol, hipStream_t stream, bool join) {
     return join_integrate(vol, stream);
 }
 
-static ot_status counter_errors(const int* c) {
-    if (c[C_OVERFLOW]) return fail(OT_ERR_CAPACITY, "[ScalableTSDFVolume] volume unit pool exhausted (max_units)");
-    if (c[C_HASHERR] & 1) return fail(OT_ERR_CAPACITY, "[ScalableTSDFVolume] unit hash table full");
-    if (c[C_HASHERR] & 2) return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] unit index out of range");
-    return OT_OK;
-}
-
-// one wave copies n <= OT_MAIL_WORDS 4-byte words into the volume's pinned coherent mailbox (plain vector stores over
-// PCIe); the caller synchronises the stream and reads vol->hmail.  One launch replaces a staged D2H copy per value
-__global__ void k_mail_words(MailSrc s, unsigned* __restrict__ out) {
-    const int i = threadIdx.x;
-    if (i < s.n) out[i] = *s.p[i];
-}
-
-ot_status mail_words(ot_tsdf* vol, const MailSrc& s, hipStream_t stream) {
-    if (s.n > MAIL_SEQ_MC) return fail(OT_ERR_INVALID_ARGUMENT, "mailbox overflow");
-    hipLaunchKernelGGL(k_mail_words, dim3(1), dim3(64), 0, stream, s, vol->hmail);
-    OT_LAUNCH_CHECK();
-    OT_HIP_TRY(hipStreamSynchronize(stream));
-    return OT_OK;
-}
-
-// The stream is polled only once the wait has lasted 20 ms (then every ~1 ms): a stream query puts commands on the
-// stream's queue, and while the host spins the queue already holds the work launched after the mailing kernel -- polling
-// every ~20 us had left ~6 us of idle GPU behind that work at each wait (host launch trace against the kernel trace,
-// tools/launch_lag.py, r05ah: the gaps before the unit sort and before the sampler).
-// Host CPU bound: the loop spins with `pause` only for the first ~50 us -- the mails the headline
-// waits for arrive within that (the units kernel ~10 us after the touch, the marching-cubes totals) -- then yields the
-// core on every check (sched_yield: a rank's other threads and RCCL's proxy threads get it), and past 2 ms sleeps
-// 20 us per check, so 8 ranks x 2 object streams waiting on a long kernel do not hold 16 cores at 100 %.
-ot_status mail_wait(const unsigned* word, unsigned seq, hipStream_t stream) {
-    using clk = std::chrono::steady_clock;
-    const clk::time_point t0 = clk::now();
-    const clk::time_point t_yield = t0 + std::chrono::microseconds(50);
-    const clk::time_point t_sleep = t0 + std::chrono::milliseconds(2);
-    clk::time_point next = t0 + std::chrono::milliseconds(20);
-    for (unsigned it = 1;; ++it) {
-        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return OT_OK;
-        const bool spin = (it & 63u) != 0;
-        if (spin && it < (1u << 20)) {  // the clock is read every 64 polls while spinning
-            __builtin_ia32_pause();
-            continue;
-        }
-        const clk::time_point now = clk::now();
-        if (now < t_yield) {
-            __builtin_ia32_pause();
-            continue;
-        }
-        it = 1u << 20;  // from here every poll reads the clock
-        if (now >= next) {  // has the stream faulted, or drained without the mail?
-            next = now + std::chrono::milliseconds(1);
-            const hipError_t q = hipStreamQuery(stream);
-            if (q == hipSuccess) {
-                if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return OT_OK;
-                return fail(OT_ERR_HIP, "mailbox: the stream drained without the kernel's mail");
-            }
-            if (q != hipErrorNotReady) OT_HIP_TRY(q);
-        }
-        if (now < t_sleep) sched_yield();
-        else std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
-}
-
-static ot_status check_errors(ot_tsdf* vol, hipStream_t stream) {
-    int c[N_COUNTERS];
-    OT_HIP_TRY(hipMemcpyAsync(c, vol->dev.counters, sizeof(c), hipMemcpyDeviceToHost, stream));
-    OT_HIP_TRY(hipStreamSynchronize(stream));
-    if (c[C_OVERFLOW]) return fail(OT_ERR_CAPACITY, "[ScalableTSDFVolume] volume unit pool exhausted (max_units)");
-    if (c[C_HASHERR] & 1) return fail(OT_ERR_CAPACITY, "[ScalableTSDFVolume] unit hash table full");
-    if (c[C_HASHERR] & 2) return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] unit index out of range");
-    return OT_OK;
-}
-
-ot_status tsdf_sorted_units(ot_tsdf* vol, hipStream_t stream, int64_t* n_units) {
-    ot_status st = tsdf_flush(vol, stream);
-    if (st != OT_OK) return st;
-    int c[N_COUNTERS];  // error flags and the unit count in one read-back (the pinned mailbox)
-    if (vol->early_frame == vol->frame_id && !vol->imported && vol->units_seq != 0) {
-        // mailed by the last batch's units kernel (settle_batch saw it): not waiting for the integrate behind it
-        st = mail_wait(vol->hmail + MAIL_SEQ_UNITS, vol->units_seq, stream);
-        if (st != OT_OK) return st;
-        std::memcpy(c, vol->hmail + OT_MAIL_WORDS, sizeof(c));
-    } else {
-        MailSrc ms;
-        ms.n = N_COUNTERS;
-        for (int i = 0; i < N_COUNTERS; ++i) ms.p[i] = (const unsigned*)vol->dev.counters + i;
-        st = mail_words(vol, ms, stream);
-        if (st != OT_OK) return st;
-        std::memcpy(c, vol->hmail, sizeof(c));
-    }
-    st = counter_errors(c);
-    if (st != OT_OK) return st;
-    int nu = (int)std::min<int64_t>(c[C_UNITS], vol->max_units);
-    *n_units = nu;
-    if (vol->sorted_frame == vol->frame_id && vol->sorted_units == nu) return OT_OK;
-    if (nu > 0) {
-        int hb[6];  // per-axis key bounds, kept by the allocating kernels (note_unit_key)
-        for (int a = 0; a < 3; ++a) {
-            hb[a] = KEY_BIAS + 1 - c[C_KNEG + a];
-            hb[3 + a] = c[C_KMAX + a] - KEY_BIAS - 1;
-        }
-        int bits[3];
-        for (int a = 0; a < 3; ++a) {
-            const long long span = (long long)hb[3 + a] - hb[a];
-            bits[a] = 1;
-            while (bits[a] < 31 && (span >> bits[a]) != 0) ++bits[a];
-        }
-        const UnitKeyPack pk{hb[0], hb[1], hb[2], bits[2], bits[1] + bits[2]};
-        const int kb = bits[0] + bits[1] + bits[2];
-        if (kb <= USORT_BITS && !g_unit_sort_radix) {
-            hipLaunchKernelGGL(k_unit_rank_sort, dim3(1), dim3(1024), 0, stream, vol->dev, nu, pk, kb, vol->sorted_ids);
-            OT_LAUNCH_CHECK();
-            vol->sorted_units = nu;
-            vol->sorted_frame = vol->frame_id;
-            return OT_OK;
-        }
-        char* ws = (char*)scratch((size_t)nu * 24 + 256, 5);
-        if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-        unsigned long long* kin = (unsigned long long*)(ws + 256);
-        unsigned long long* kout = kin + nu;
-        unsigned* vin = (unsigned*)(kout + nu);
-        hipLaunchKernelGGL(k_pack_unit_keys, dim3((nu + 255) / 256), dim3(256), 0, stream, vol->dev, nu, pk, kin, vin);
-        OT_LAUNCH_CHECK();
-        st = sort_pairs_u64_u32(kin, kout, vin, vol->sorted_ids, (size_t)nu, std::min(63, bits[0] + bits[1] + bits[2]),
-                                stream, 3);
-        if (st != OT_OK) return st;
-    }
-    vol->sorted_units = nu;
-    vol->sorted_frame = vol->frame_id;
-    return OT_OK;
-}
-
 }  // namespace ot
 
 using namespace ot;
 
-namespace ot {
-__global__ __launch_bounds__(256) void k_tsdf_clear(TsdfDev d, int64_t cap) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += (int64_t)gridDim.x * 256) {
-        d.hkeys[i] = ~0ull;
-        d.hvals[i] = -1;
-        d.fmask[i] = 0ull;
-    }
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < N_COUNTERS) d.counters[threadIdx.x] = 0;
-        if (threadIdx.x < 4) d.stats[threadIdx.x] = 0ull;
-    }
-}
-}  // namespace ot
-
 extern "C" {
-
-ot_status ot_tsdf_create(double voxel_length, double sdf_trunc, int32_t color_type, int32_t unit_res, int32_t stride,
-                         int64_t max_units, ot_tsdf** out) {
-    if (!out) return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] out is NULL");
-    *out = nullptr;
-    if (!(voxel_length > 0.0) || !(sdf_trunc > 0.0))
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] voxel_length and sdf_trunc must be positive");
-    if (unit_res != UNIT_RES)
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] only volume_unit_resolution=16 is supported");
-    if (stride < 1) return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] depth_sampling_stride must be >= 1");
-    if (color_type != OT_COLOR_NONE && color_type != OT_COLOR_RGB8)
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] unsupported color_type (NoColor or RGB8)");
-    if (max_units <= 0) max_units = 32768;
-    if (max_units > (1 << 24)) return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] max_units too large");
-    ot_tsdf* v = new ot_tsdf();
-    (void)hipGetDevice(&v->device);
-    v->voxel_length = voxel_length;
-    v->sdf_trunc = sdf_trunc;
-    v->unit_length = voxel_length * (double)UNIT_RES;
-    v->color_type = color_type;
-    v->stride = stride;
-    v->max_units = max_units;
-    int64_t cap = 1;
-    while (cap < 4 * max_units) cap <<= 1;
-    v->hash_cap = cap;
-    TsdfDev& d = v->dev;
-    d.hash_mask = (int)(cap - 1);
-    d.max_units = (int)max_units;
-    auto cleanup = [&](hipError_t e) {
-        set_error(std::string("[ScalableTSDFVolume] allocation failed: ") + hipGetErrorString(e));
-        ot_tsdf_destroy(v);
-        return OT_ERR_HIP;
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&d.hkeys, sizeof(unsigned long long) * cap)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.hvals, sizeof(int) * cap)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.counters, sizeof(int) * N_COUNTERS)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.stats, sizeof(unsigned long long) * 4)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.unit_keys, sizeof(int) * 3 * max_units)) != hipSuccess) return cleanup(e);
-    // RGB8 volumes keep colour at Open3D's precision (float64, 128-KiB records) unless set_color_precision(32)
-    v->color64 = color_type == OT_COLOR_RGB8;
-    d.color64 = v->color64 ? 1 : 0;
-    d.unit_floats = v->color64 ? UNIT_FLOATS_C64 : UNIT_FLOATS;
-    if ((e = hipMalloc(&d.vox, sizeof(float) * (size_t)d.unit_floats * max_units)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&v->sorted_ids, sizeof(unsigned) * max_units)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.fmask, sizeof(unsigned long long) * cap)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.bslots, sizeof(int) * cap)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.work, sizeof(UnitWork) * cap)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&v->bset[0].bframes, sizeof(BatchFrame) * MAX_BATCH)) != hipSuccess) return cleanup(e);
-    // coherent: k_copy_frames reads the staging straight from host memory, and non-coherent host memory may be cached
-    // by the GPU (the halves are rewritten every other batch)
-    if ((e = hipHostMalloc(&v->hbframes, sizeof(BatchFrame) * MAX_BATCH * 2, hipHostMallocCoherent)) != hipSuccess)
-        return cleanup(e);
-    if ((e = hipHostMalloc(&v->hmail, sizeof(unsigned) * 2 * OT_MAIL_WORDS, hipHostMallocCoherent)) != hipSuccess)
-        return cleanup(e);
-    std::memset(v->hmail, 0, sizeof(unsigned) * 2 * OT_MAIL_WORDS);  // sequence words start below every seq sent (>= 1)
-    ot_status st = ot_tsdf_reset(v);
-    if (st != OT_OK) {
-        ot_tsdf_destroy(v);
-        return st;
-    }
-    *out = v;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_destroy(ot_tsdf* v) {
-    if (!v) return OT_OK;
-    (void)hipDeviceSynchronize();
-    TsdfDev& d = v->dev;
-    ot_tsdf_set_profiling(v, 0);
-    void* ptrs[] = {d.hkeys, d.hvals, d.counters, d.stats, d.unit_keys, d.vox, v->mult, v->sorted_ids, v->mesh.ws,
-                    v->mesh.v, v->mesh.c, v->mesh.t, v->mesh.vk, v->mesh.tk, v->mesh.vown, d.fmask, d.bslots, d.work,
-                    v->cloud.ws, v->wcount, v->bset[0].bframes, v->bset[0].bdc, v->bset[1].bframes, v->bset[1].bdc,
-                    v->bset[1].work, v->tmask};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (v->hbframes) (void)hipHostFree(v->hbframes);
-    if (v->hmail) (void)hipHostFree(v->hmail);
-    if (v->ev_fork) (void)hipEventDestroy(v->ev_fork);
-    if (v->ev_join) (void)hipEventDestroy(v->ev_join);
-    if (v->ev_normals) (void)hipEventDestroy(v->ev_normals);
-    if (v->ev_made) (void)hipEventDestroy(v->ev_made);
-    if (v->ev_dfr) (void)hipEventDestroy(v->ev_dfr);
-    if (v->side) (void)hipStreamDestroy(v->side);
-    if (v->istream) (void)hipStreamDestroy(v->istream);
-    for (auto& b : v->bset) {
-        if (b.ev_units) (void)hipEventDestroy(b.ev_units);
-        if (b.ev_done) (void)hipEventDestroy(b.ev_done);
-    }
-    delete v;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_reset(ot_tsdf* v) {
-    if (!v) return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume::Reset] volume is NULL");
-    TsdfDev& d = v->dev;
-    OT_HIP_TRY(hipDeviceSynchronize());  // queued work on the volume (deferred normals included) first
-    v->normals_pending = false;
-    v->last_set = -1;
-    OT_HIP_TRY(hipMemset(d.hkeys, 0xFF, sizeof(unsigned long long) * v->hash_cap));
-    OT_HIP_TRY(hipMemset(d.hvals, 0xFF, sizeof(int) * v->hash_cap));
-    OT_HIP_TRY(hipMemset(d.fmask, 0, sizeof(unsigned long long) * v->hash_cap));
-    OT_HIP_TRY(hipMemset(d.counters, 0, sizeof(int) * N_COUNTERS));
-    OT_HIP_TRY(hipMemset(d.stats, 0, sizeof(unsigned long long) * 4));
-    OT_HIP_TRY(hipDeviceSynchronize());
-    v->batch_pc = C_BATCH_PAIRS;
-    v->frame_id = 0;
-    v->imported = false;
-    v->early_frame = -1;
-    v->pending.clear();
-    v->dfr_on = false;  // a deferred batch's integrate belongs to the old contents (its work list is stale now)
-    v->stat_batches = v->stat_unit_batches = v->stat_fresh = v->stat_prev_units = 0;
-    v->sorted_frame = -1;
-    v->sorted_units = -1;
-    v->mesh.nv = v->mesh.nt = 0;
-    v->mesh.valid = false;
-    v->cloud.valid = false;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_reset_async(ot_tsdf* v, void* stream_) {
-    if (!v) return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume::Reset] volume is NULL");
-    hipStream_t stream = S(stream_);
-    ot_status st = tsdf_flush(v, stream);  // queued frames belong to the old contents: apply, then clear
-    if (st != OT_OK) return st;
-    st = wait_normals(v, stream);  // the last mesh's deferred normals may still read the volume
-    if (st != OT_OK) return st;
-    // the hash table, frame masks, counters and statistics in one launch (six fill commands cost ~5 us of host time
-    // each, on one object's critical path)
-    const unsigned blocks = (unsigned)std::min<int64_t>((v->hash_cap + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_tsdf_clear, dim3(blocks), dim3(256), 0, stream, v->dev, (int64_t)v->hash_cap);
-    OT_LAUNCH_CHECK();
-    v->batch_pc = C_BATCH_PAIRS;
-    v->frame_id = 0;
-    v->imported = false;
-    v->early_frame = -1;
-    v->last_batch_slots = -1;
-    v->stat_batches = v->stat_unit_batches = v->stat_fresh = v->stat_prev_units = 0;
-    v->sorted_frame = -1;
-    v->sorted_units = -1;
-    v->mesh.nv = v->mesh.nt = 0;
-    v->mesh.valid = false;
-    v->cloud.valid = false;
-    return OT_OK;
-}
 
 ot_status ot_tsdf_integrate(ot_tsdf* vol, const float* depth, const uint8_t* color, const ot_intrinsics* in,
                             const double extrinsic[16], void* stream) {
@@ -2712,408 +2039,6 @@ ot_status ot_tsdf_integrate_u16_frames(ot_tsdf* vol, int32_t n, const uint16_t* 
 ot_status ot_tsdf_flush(ot_tsdf* vol, void* stream) {
     if (!vol) return fail(OT_ERR_INVALID_ARGUMENT, "volume is NULL");
     return tsdf_flush(vol, S(stream));
-}
-
-ot_status ot_tsdf_pending_frames(const ot_tsdf* vol, int32_t* n_host) {
-    if (!vol || !n_host) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    *n_host = (int32_t)vol->pending.size();
-    return OT_OK;
-}
-
-ot_status ot_tsdf_set_batch(ot_tsdf* vol, int32_t max_frames) {
-    if (!vol || max_frames < 1) return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] batch must be >= 1");
-    vol->batch_max = max_frames;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_set_frontend_overlap(ot_tsdf* vol, int32_t mode) {
-    if (!vol || mode < -1 || mode > 1)
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] front-end overlap mode must be -1, 0 or 1");
-    // the mode changes only on a drained volume: queued frames would be staged on whichever stream this call named,
-    // not the one their producers ran on -- flush or read the volume on the frames' stream first
-    if (!vol->pending.empty())
-        return fail(OT_ERR_INVALID_ARGUMENT,
-                    "[ScalableTSDFVolume] front-end overlap can change only with no queued frames (flush first)");
-    if (vol->istream) OT_HIP_TRY(hipStreamSynchronize(vol->istream));  // a running integrate of the old mode
-    vol->last_set = -1;
-    vol->overlap_mode = mode;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_num_units(ot_tsdf* vol, int64_t* n, void* stream_) {
-    if (!vol || !n) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    hipStream_t stream = S(stream_);
-    ot_status st = tsdf_flush(vol, stream);  // queued frames, on the caller's stream
-    if (st != OT_OK) return st;
-    if (vol->dev.shard_world > 1) {  // a shard counts its own units (halo units are not exported)
-        const unsigned* ids = nullptr;
-        return export_list(vol, stream, &ids, n);
-    }
-    int nu = 0;
-    OT_HIP_TRY(hipMemcpyAsync(&nu, vol->dev.counters + C_UNITS, sizeof(int), hipMemcpyDeviceToHost, stream));
-    OT_HIP_TRY(hipStreamSynchronize(stream));
-    *n = std::min<int64_t>(nu, vol->max_units);
-    return OT_OK;
-}
-
-ot_status ot_tsdf_batch_stats(ot_tsdf* vol, int64_t* batches, int64_t* unit_batches, int64_t* new_units) {
-    if (!vol) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    if (batches) *batches = vol->stat_batches;  // batches run (frames still queued are not counted: flush first)
-    if (unit_batches) *unit_batches = vol->stat_unit_batches;
-    if (new_units) *new_units = vol->stat_fresh;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_counters(ot_tsdf* vol, int64_t* updates, int64_t* unit_integrations, void* stream_) {
-    if (!vol) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    hipStream_t stream = S(stream_);
-    ot_status st = tsdf_flush(vol, stream);
-    if (st != OT_OK) return st;
-    unsigned long long s[4];
-    OT_HIP_TRY(hipMemcpyAsync(s, vol->dev.stats, sizeof(s), hipMemcpyDeviceToHost, stream));
-    OT_HIP_TRY(hipStreamSynchronize(stream));
-    if (updates) *updates = (int64_t)s[S_UPDATES];
-    if (unit_integrations) *unit_integrations = (int64_t)s[S_UNIT_INTEGRATIONS];
-    return OT_OK;
-}
-
-ot_status ot_tsdf_set_color_precision(ot_tsdf* vol, int32_t bits) {
-    if (!vol || (bits != 32 && bits != 64))
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] colour precision must be 32 or 64 bits");
-    int nu = 0;
-    OT_HIP_TRY(hipMemcpy(&nu, vol->dev.counters + C_UNITS, sizeof(int), hipMemcpyDeviceToHost));
-    if (nu != 0 || !vol->pending.empty())
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] set the colour precision before the first integrate");
-    // NoColor volumes keep no colour state: the float32 record (zero colour planes) whatever the precision
-    const bool c64 = bits == 64 && vol->color_type == OT_COLOR_RGB8;
-    if (c64 != vol->color64) {  // the record stride changes: reallocate the (still empty) pool
-        const int uf = c64 ? UNIT_FLOATS_C64 : UNIT_FLOATS;
-        OT_HIP_TRY(hipDeviceSynchronize());
-        // the new pool first: if the allocation fails the volume keeps its old, consistent layout
-        float* pool = nullptr;
-        OT_HIP_TRY(hipMalloc(&pool, sizeof(float) * (size_t)uf * vol->max_units));
-        (void)hipFree(vol->dev.vox);
-        vol->dev.vox = pool;
-        vol->dev.unit_floats = uf;
-        vol->dev.color64 = c64 ? 1 : 0;
-        vol->color64 = c64;
-    }
-    return OT_OK;
-}
-
-ot_status ot_tsdf_get_color_precision(const ot_tsdf* vol, int32_t* bits) {
-    if (!vol || !bits) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    *bits = vol->color64 ? 64 : 32;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_set_profiling(ot_tsdf* vol, int32_t enable) {
-    if (!vol) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    vol->profiling = enable != 0;
-    vol->prof_ms = vol->prof_fe_ms = 0.0;
-    vol->prof_launches = vol->prof_fe_batches = 0;
-    for (auto* lst : {&vol->prof_events, &vol->prof_fe_events}) {
-        for (auto& e : *lst) {
-            (void)hipEventDestroy(e.first);
-            (void)hipEventDestroy(e.second);
-        }
-        lst->clear();
-    }
-    return OT_OK;
-}
-
-// accumulate (and release) an event-pair list into (ms, count)
-static ot_status drain_events(std::vector<std::pair<hipEvent_t, hipEvent_t>>& lst, double& ms_acc, int64_t& n_acc) {
-    for (auto& e : lst) {
-        OT_HIP_TRY(hipEventSynchronize(e.second));
-        float ms = 0.0f;
-        OT_HIP_TRY(hipEventElapsedTime(&ms, e.first, e.second));
-        ms_acc += ms;
-        n_acc += 1;
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
-    lst.clear();
-    return OT_OK;
-}
-
-ot_status ot_tsdf_kernel_time(ot_tsdf* vol, double* total_ms, int64_t* launches) {
-    if (!vol) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    ot_status st = tsdf_flush(vol, nullptr);
-    if (st != OT_OK) return st;
-    if ((st = drain_events(vol->prof_events, vol->prof_ms, vol->prof_launches)) != OT_OK) return st;
-    if (total_ms) *total_ms = vol->prof_ms;
-    if (launches) *launches = vol->prof_launches;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_frontend_time(ot_tsdf* vol, double* total_ms, int64_t* batches) {
-    if (!vol) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    ot_status st = tsdf_flush(vol, nullptr);
-    if (st != OT_OK) return st;
-    if ((st = drain_events(vol->prof_fe_events, vol->prof_fe_ms, vol->prof_fe_batches)) != OT_OK) return st;
-    if (total_ms) *total_ms = vol->prof_fe_ms;
-    if (batches) *batches = vol->prof_fe_batches;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_export_units(ot_tsdf* vol, int64_t capacity, int32_t* keys, float* tsdf, float* weight, float* color,
-                               void* stream) {
-    if (!vol) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    int64_t nu = 0;
-    const unsigned* ids = nullptr;
-    ot_status st = export_list(vol, S(stream), &ids, &nu);
-    if (st != OT_OK) return st;
-    if (nu > capacity) return fail(OT_ERR_CAPACITY, "[ScalableTSDFVolume] export: more units than the output capacity");
-    if (nu == 0) return OT_OK;
-    if (vol->color64)
-        hipLaunchKernelGGL((k_export<double, float>), dim3((unsigned)nu), dim3(256), 0, S(stream), vol->dev, ids, keys,
-                           tsdf, weight, color);
-    else
-        hipLaunchKernelGGL((k_export<float, float>), dim3((unsigned)nu), dim3(256), 0, S(stream), vol->dev, ids, keys,
-                           tsdf, weight, color);
-    OT_LAUNCH_CHECK();
-    OT_HIP_TRY(hipStreamSynchronize(S(stream)));
-    return OT_OK;
-}
-
-ot_status ot_tsdf_export_color64(ot_tsdf* vol, int64_t capacity, double* color, void* stream) {
-    if (!vol || !color) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    int64_t nu = 0;
-    const unsigned* ids = nullptr;
-    ot_status st = export_list(vol, S(stream), &ids, &nu);
-    if (st != OT_OK) return st;
-    if (nu > capacity) return fail(OT_ERR_CAPACITY, "[ScalableTSDFVolume] export: more units than the output capacity");
-    if (nu == 0) return OT_OK;
-    if (vol->color64)
-        hipLaunchKernelGGL((k_export<double, double>), dim3((unsigned)nu), dim3(256), 0, S(stream), vol->dev, ids,
-                           nullptr, nullptr, nullptr, color);
-    else  // float32 colour state (or NoColor's zero planes) widens exactly
-        hipLaunchKernelGGL((k_export<float, double>), dim3((unsigned)nu), dim3(256), 0, S(stream), vol->dev, ids,
-                           nullptr, nullptr, nullptr, color);
-    OT_LAUNCH_CHECK();
-    OT_HIP_TRY(hipStreamSynchronize(S(stream)));
-    return OT_OK;
-}
-
-// test / diagnostic hook (not part of the drop-in boundary): the volume's raw u64 stats[4] (0 voxel updates,
-// 1 unit integrations; 2, 3 unused)
-ot_status otx_tsdf_stats(ot_tsdf* vol, uint64_t* out4) {
-    if (!vol || !out4) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    ot_status st = tsdf_flush(vol, nullptr);
-    if (st != OT_OK) return st;
-    OT_HIP_TRY(hipMemcpy(out4, vol->dev.stats, sizeof(uint64_t) * 4, hipMemcpyDeviceToHost));
-    return OT_OK;
-}
-
-// test hook: the integrate's slice granularity (-1 = by the batch's estimated unit count, 0 = 4 voxels per lane along z
-// always, 1 = 2 always; >= 2: the deferred integrate takes the fine slices below that many units, a threshold sweep):
-// A/B timing and the parity of both instantiations
-ot_status otx_integrate_fine(int32_t mode) {
-    g_int_fine = mode < 0 ? -1 : (mode == 1 ? 1 : 0);
-    g_fine_units = mode >= 2 ? mode : -1;
-    return OT_OK;
-}
-
-// test hook: waves per workgroup of the coarse integrate (-1 = the default rule of integrate_form; 1, 2 or 4 forced at
-// every table size): A/B timing and the parity of the three forms
-ot_status otx_integrate_workgroup(int32_t waves) {
-    if (waves != -1 && waves != 1 && waves != 2 && waves != 4)
-        return fail(OT_ERR_INVALID_ARGUMENT, "otx_integrate_workgroup: -1, 1, 2 or 4 waves");
-    g_int_wg = waves;
-    return OT_OK;
-}
-
-// test hook: the batch touch's staging-only workgroups per frame group (-1 = two per touch tile, the default;
-// 0 = every touch workgroup stages a share first): A/B timing and the parity of both forms
-ot_status otx_touch_stage_blocks(int32_t blocks) {
-    if (blocks > 4096) return fail(OT_ERR_INVALID_ARGUMENT, "otx_touch_stage_blocks: at most 4096");
-    g_stage_blocks = blocks < 0 ? -1 : blocks;
-    return OT_OK;
-}
-
-// test hook: frames per touch workgroup (1..64, default TF): A/B timing and the parity of other groupings
-ot_status otx_touch_frames(int32_t tf) {
-    if (tf < 1 || tf > MAX_BATCH) return fail(OT_ERR_INVALID_ARGUMENT, "otx_touch_frames: 1..64");
-    g_touch_tf = tf;
-    return OT_OK;
-}
-
-// test hook: 1 = sort units with the radix sort at every key width (the rank sort's parity test), 0 = default
-ot_status otx_unit_sort_radix(int32_t on) {
-    g_unit_sort_radix = on != 0;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_set_shard(ot_tsdf* vol, int32_t rank, int32_t world) {
-    if (!vol || world < 1 || rank < 0 || rank >= world)
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] shard needs 0 <= rank < world");
-    int nu = 0;
-    OT_HIP_TRY(hipMemcpy(&nu, vol->dev.counters + C_UNITS, sizeof(int), hipMemcpyDeviceToHost));
-    if (nu != 0 || !vol->pending.empty())
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] set the shard before the first integrate");
-    vol->dev.shard_rank = rank;
-    vol->dev.shard_world = world;
-    vol->dev.shard_mode = SHARD_BLOCKS;
-    // ownership blocks: 4^3 units up to 4 ranks, 2^3 beyond (configs[1] scan, 5 mm: largest shard / mean 1.09 / 1.13 /
-    // 1.09 at 2 / 4 / 8 ranks; border rows sent 0.42 / 0.25 / 0.24 of an all-gather's)
-    vol->dev.shard_shift = world <= 4 ? 2 : 1;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_set_shard_sector(ot_tsdf* vol, int32_t rank, int32_t world, double cx, double cy) {
-    if (!vol || world < 1 || rank < 0 || rank >= world || !std::isfinite(cx) || !std::isfinite(cy))
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] shard needs 0 <= rank < world and a finite centre");
-    const double hx = std::nearbyint(2.0 * cx / vol->unit_length), hy = std::nearbyint(2.0 * cy / vol->unit_length);
-    if (std::fabs(hx) > (double)(1 << 22) || std::fabs(hy) > (double)(1 << 22))
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] sector centre out of the unit key range");
-    ot_status st = ot_tsdf_set_shard(vol, rank, world);
-    if (st != OT_OK) return st;
-    vol->dev.shard_mode = SHARD_SECTORS;
-    vol->dev.shard_cx2 = (int)hx;
-    vol->dev.shard_cy2 = (int)hy;
-    return OT_OK;
-}
-
-ot_status otx_integrate_depth(int32_t kt) {
-    if (kt != -1 && (kt < 1 || kt > 3)) return fail(OT_ERR_INVALID_ARGUMENT, "integrate pipeline depth must be -1 or 1..3");
-    g_int_depth = kt;
-    return OT_OK;
-}
-
-ot_status otx_defer_integrate(int32_t mode) {
-    if (mode < -1 || mode > 1) return fail(OT_ERR_INVALID_ARGUMENT, "deferred integrate mode must be -1, 0 or 1");
-    g_defer = mode;
-    return OT_OK;
-}
-
-ot_status otx_split_frontend(int32_t mode) {
-    if (mode < -1 || mode > 1) return fail(OT_ERR_INVALID_ARGUMENT, "split front end mode must be -1, 0 or 1");
-    g_split = mode;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_set_shard_block(ot_tsdf* vol, int32_t log2_units) {
-    if (!vol || log2_units < 0 || log2_units > 8)
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] shard block must be 2^0 .. 2^8 units per axis");
-    int nu = 0;
-    OT_HIP_TRY(hipMemcpy(&nu, vol->dev.counters + C_UNITS, sizeof(int), hipMemcpyDeviceToHost));
-    if (nu != 0 || !vol->pending.empty())
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] set the shard before the first integrate");
-    vol->dev.shard_shift = log2_units;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_border_destinations(const ot_tsdf* vol, int64_t n, const int32_t* keys, int64_t* dest_mask,
-                                      void* stream) {
-    if (!vol || n < 0 || (n > 0 && (!keys || !dest_mask)) || vol->dev.shard_world > 64)
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] border_destinations: invalid arguments");
-    if (n == 0) return OT_OK;
-    hipLaunchKernelGGL(k_border_dest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), vol->dev, n, keys,
-                       (unsigned long long*)dest_mask);
-    OT_LAUNCH_CHECK();
-    return OT_OK;
-}
-
-}  // extern "C"
-
-template <typename CT>
-static ot_status import_units(ot_tsdf* vol, int64_t n, const int32_t* keys, const float* tsdf, const float* weight,
-                              const CT* color, hipStream_t stream) {
-    if (!vol || n < 0 || (n > 0 && (!keys || !tsdf || !weight)))
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] import: invalid arguments");
-    const bool rgb8 = vol->color_type == OT_COLOR_RGB8;
-    if (rgb8 && vol->color64 != (sizeof(CT) == 8))
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] import: colour dtype does not match the volume's "
-                                             "colour precision");
-    ot_status st = tsdf_flush(vol, stream);
-    if (st != OT_OK) return st;
-    if (n == 0) return OT_OK;
-    st = reserve_units(vol, n, stream);  // the pool grows instead of dropping imported units
-    if (st != OT_OK) return st;
-    if (rgb8)
-        hipLaunchKernelGGL(k_import<CT>, dim3((unsigned)n), dim3(256), 0, stream, vol->dev, keys, tsdf, weight, color);
-    else  // NoColor: float32 record, zero colour planes
-        hipLaunchKernelGGL(k_import<float>, dim3((unsigned)n), dim3(256), 0, stream, vol->dev, keys, tsdf, weight,
-                           (const float*)nullptr);
-    OT_LAUNCH_CHECK();
-    vol->sorted_units = -1;  // the sorted-unit cache no longer matches
-    vol->imported = true;    // arbitrary state: the IEEE-division integrate from now on
-    vol->stat_prev_units = -1;
-    vol->mesh.valid = false;
-    vol->cloud.valid = false;
-    st = check_errors(vol, stream);
-    if (st != OT_OK) return st;
-    OT_HIP_TRY(hipStreamSynchronize(stream));
-    return OT_OK;
-}
-
-extern "C" {
-
-ot_status ot_tsdf_import_units(ot_tsdf* vol, int64_t n, const int32_t* keys, const float* tsdf, const float* weight,
-                               const float* color, void* stream) {
-    return import_units<float>(vol, n, keys, tsdf, weight, color, S(stream));
-}
-
-ot_status ot_tsdf_import_units_color64(ot_tsdf* vol, int64_t n, const int32_t* keys, const float* tsdf,
-                                       const float* weight, const double* color, void* stream) {
-    return import_units<double>(vol, n, keys, tsdf, weight, color, S(stream));
-}
-
-ot_status ot_tsdf_export_border(ot_tsdf* vol, int64_t capacity, int32_t* keys, float* tsdf, float* weight, void* color,
-                                int64_t* n_exported_host, void* stream) {
-    if (!vol || !keys || !tsdf || !weight || !n_exported_host) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
-    *n_exported_host = 0;
-    int64_t no = 0;  // the own units (halo units imported earlier are not this shard's border)
-    const unsigned* own = nullptr;
-    ot_status st = export_list(vol, S(stream), &own, &no);
-    if (st != OT_OK) return st;
-    if (no == 0) return OT_OK;
-    if (no > capacity) return fail(OT_ERR_CAPACITY, "[ScalableTSDFVolume] export: more units than the output capacity");
-    if (no > 0) {
-        if (vol->color_type != OT_COLOR_RGB8)  // NoColor: no colour rows (the caller's buffer is left as it is)
-            hipLaunchKernelGGL(k_export_border<float>, dim3((unsigned)no), dim3(256), 0, S(stream), vol->dev, own,
-                               keys, tsdf, weight, (float*)nullptr);
-        else if (vol->color64)
-            hipLaunchKernelGGL(k_export_border<double>, dim3((unsigned)no), dim3(256), 0, S(stream), vol->dev, own,
-                               keys, tsdf, weight, (double*)color);
-        else
-            hipLaunchKernelGGL(k_export_border<float>, dim3((unsigned)no), dim3(256), 0, S(stream), vol->dev, own,
-                               keys, tsdf, weight, (float*)color);
-        OT_LAUNCH_CHECK();
-    }
-    OT_HIP_TRY(hipStreamSynchronize(S(stream)));
-    *n_exported_host = no;
-    return OT_OK;
-}
-
-ot_status ot_tsdf_import_border(ot_tsdf* vol, int64_t n, const int32_t* keys, const float* tsdf, const float* weight,
-                                const void* color, void* stream_) {
-    hipStream_t stream = S(stream_);
-    if (!vol || n < 0 || (n > 0 && (!keys || !tsdf || !weight)))
-        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume] import_border: invalid arguments");
-    ot_status st = tsdf_flush(vol, stream);
-    if (st != OT_OK) return st;
-    if (n == 0) return OT_OK;
-    st = reserve_units(vol, n, stream);  // halo units: room for every row (a superset of those kept)
-    if (st != OT_OK) return st;
-    const void* c = vol->color_type == OT_COLOR_RGB8 ? color : nullptr;
-    if (vol->color64)  // (only RGB8 volumes store float64 colour)
-        hipLaunchKernelGGL(k_import_border<double>, dim3((unsigned)n), dim3(256), 0, stream, vol->dev, keys, tsdf,
-                           weight, (const double*)c);
-    else
-        hipLaunchKernelGGL(k_import_border<float>, dim3((unsigned)n), dim3(256), 0, stream, vol->dev, keys, tsdf,
-                           weight, (const float*)c);
-    OT_LAUNCH_CHECK();
-    vol->sorted_units = -1;
-    vol->imported = true;  // halo units hold other shards' state (read by marching cubes; kept exact anyway)
-    vol->stat_prev_units = -1;
-    vol->mesh.valid = false;
-    vol->cloud.valid = false;
-    st = check_errors(vol, stream);
-    if (st != OT_OK) return st;
-    OT_HIP_TRY(hipStreamSynchronize(stream));
-    return OT_OK;
 }
 
 }  // extern "C"

@@ -130,6 +130,80 @@ def test_split_frontend_forced(pkg, O, gpu, synth, defer):
         L.call("otx_defer_integrate", -1)
 
 
+def _integrate_pairs(pkg, synth, vol, before_batch):
+    """the orbit in batches of 2 (the volume's batch_frames; the second frame of a pair flushes it without joining, so a
+    deferred batch stays pending); before_batch(b) runs ahead of batch b's frames"""
+    depth, color, ext = _frames(synth, WIDE, ORBIT)
+    for b in range(len(ORBIT) // 2):
+        before_batch(b)
+        s = slice(2 * b, 2 * b + 2)
+        _integrate(pkg, vol, WIDE, depth[s], color[s], ext[s])
+
+
+@pytest.mark.parametrize("defers", [(1, 0, 1), (1, 1, 0), (0, 1, 1)])
+def test_defer_mode_changes_between_batches(pkg, O, gpu, synth, defers):
+    """Three batches of 2 with the split front end, otx_defer_integrate set per batch (between batches, nothing flushes):
+    a pending deferred batch that the next batch does not fuse with is launched alone before that batch restages
+    anything, so every sequence gives the oracle's volume.  (Before integrate_batch owned the hand-over, (1, 0, 1) left
+    batch 0 pending behind the direct batch 1, which restaged its set: the third batch then integrated batch 1's frames
+    a second time and batch 0 was lost.)"""
+    L = pkg._lib
+    L.call("otx_split_frontend", 1)
+    try:
+        vol = _volume(pkg, True, 2)
+        _integrate_pairs(pkg, synth, vol, lambda b: L.call("otx_defer_integrate", defers[b]))
+        assert _compare(vol, _oracle(O, synth, WIDE, ORBIT, True), True) > 100
+    finally:
+        L.call("otx_split_frontend", -1)
+        L.call("otx_defer_integrate", -1)
+
+
+def test_overlap_set_behind_a_deferred_batch(pkg, O, gpu, synth):
+    """ot_tsdf_set_frontend_overlap(1) through the C API (the facade would flush first) while the first batch is still
+    deferred: the next batch runs double-buffered and launches the deferred one alone first."""
+    L = pkg._lib
+    L.call("otx_split_frontend", 1)
+    L.call("otx_defer_integrate", 1)
+    try:
+        vol = _volume(pkg, True, 2)
+
+        def before_batch(b):
+            if b == 1:
+                L.call("ot_tsdf_set_frontend_overlap", vol._h, 1)
+
+        _integrate_pairs(pkg, synth, vol, before_batch)
+        assert _compare(vol, _oracle(O, synth, WIDE, ORBIT, True), True) > 100
+    finally:
+        L.call("otx_split_frontend", -1)
+        L.call("otx_defer_integrate", -1)
+
+
+@pytest.mark.parametrize("reset", ["sync", "async"])
+def test_reset_behind_a_deferred_scan(pkg, O, gpu, synth, reset):
+    """A deferred scan (its last batch still pending), then the synchronous reset (ot_tsdf_reset drops the pending batch
+    with the old contents) or the stream-ordered one (it integrates it first), then the scan again: the oracle's volume
+    and counters both times -- both resets return the host state to the same start."""
+    import torch
+
+    L = pkg._lib
+    L.call("otx_split_frontend", 1)
+    L.call("otx_defer_integrate", 1)
+    try:
+        vol = _volume(pkg, True, 2)
+        _integrate_pairs(pkg, synth, vol, lambda b: None)
+        if reset == "sync":
+            torch.cuda.synchronize()
+            L.call("ot_tsdf_reset", vol._h)
+            vol._keep.clear()
+        else:
+            vol.reset()
+        _integrate_pairs(pkg, synth, vol, lambda b: None)
+        assert _compare(vol, _oracle(O, synth, WIDE, ORBIT, True), True) > 100
+    finally:
+        L.call("otx_split_frontend", -1)
+        L.call("otx_defer_integrate", -1)
+
+
 @pytest.mark.parametrize("depth", [1, 2, 3])
 def test_fine_slices_forced(pkg, O, gpu, synth, depth):
     L = pkg._lib
