@@ -40,6 +40,14 @@ constexpr int N_COUNTERS = 16;
 // stats[] slots (u64)
 constexpr int S_UPDATES = 0;
 constexpr int S_UNIT_INTEGRATIONS = 1;
+// Wave-frames the slice pre-test took out of the coarse integrate's frame masks: counted over S_DROP_LINES words a
+// cache line apart (one add per wave, the word by the workgroup's index -- tens of thousands of waves a launch on one
+// more shared word queued behind one another in memory), summed into slot S_PRETEST_DROPPED by the read-out
+constexpr int S_PRETEST_DROPPED = 2;
+constexpr int S_DROP_BASE = 8, S_DROP_LINES = 256, S_DROP_STRIDE = 8;
+// the integrate's voxel updates, spread the same way (lines of their own) and summed into S_UPDATES by the read-outs
+constexpr int S_UPD_BASE = S_DROP_BASE + S_DROP_LINES * S_DROP_STRIDE;
+constexpr int N_STATS = S_UPD_BASE + S_DROP_LINES * S_DROP_STRIDE;
 
 struct TsdfDev {
     unsigned long long* hkeys;
@@ -201,6 +209,11 @@ struct IntegrateParams {
     float proj_eps;  // certified fast projection: |u - rint(u)| > proj_eps decides floor and bounds exactly
     int rcp_hi;      // FAST kernels: the largest weight + 1 of the batch (frames since reset + the batch's), <= RCP_N
     double unit_len;
+    // slice pre-test (slice_pretest.h): the batch's tile-max depth maps, frame f's at tmax + f * tmax_tiles; nullptr: none
+    // (the batch was not staged in full, or the pre-test is off), and the integrate is the one without it
+    const unsigned* tmax;
+    int tmax_tiles;  // tiles per frame
+    int tmax_words;  // the maps' words in all (frames x tiles: the gathers' range check)
 };
 
 // parameters of the touch kernels (tsdf.hip make_touch_params)
@@ -217,6 +230,8 @@ struct BatchTouchParams {
     int tf;             // frames per group (TF)
     int sample_stage;   // split front end (stage_blocks < 0): each stride sample stores its own pixel's staged record
                         // (a replay touch reads it; k_stage_tiles stages only the owned units' footprints)
+    unsigned* tmax;     // the set's tile-max depth maps, written by the staging (frame f's at tmax + f * tiles); nullptr: none
+    int H;
 };
 
 // parameters of the split front end's tile-mask kernel (tsdf.hip make_stage_params)
@@ -243,6 +258,7 @@ enum class BatchMode { Direct, Overlap, Deferred };
 struct BatchPlan {
     BatchMode mode = BatchMode::Direct;
     bool split = false;     // split front end: touch without staging -> units -> tile mask -> staging of the marked tiles
+    bool pretest = false;   // the staging builds the tile-max maps and the coarse integrate drops idle frames per slice
     int set = 0;            // the batch's staging set (ot_tsdf::bset; its work list: tsdf.hip set_work -- resolved at each
                             // launch, pool growth reallocates the lists)
     int* wcount = nullptr;  // where the integrate reads the work list's length: the batch's pair counter, or ...
@@ -341,6 +357,8 @@ struct ot_tsdf {
         ot::BatchFrame* bframes = nullptr;  // device [MAX_BATCH]
         uint2* bdc = nullptr;               // device [batch][h][w] packed (depth, colour) records
         int64_t cap = 0;                    // pixels (frames * h * w) the buffer holds
+        unsigned* tmax = nullptr;           // device [batch][tile rows][tile columns]: largest staged depth per 8 x 8
+        int64_t tmax_cap = 0;               // pixel tile (slice_pretest.h), words the buffer holds
         void* work = nullptr;               // UnitWork [hash_cap]; set 0 uses dev.work
         hipEvent_t ev_units = nullptr;      // the set's units kernel (its integrate waits for it)
         hipEvent_t ev_done = nullptr;       // the set's integrate (the set's next front end waits for it)
@@ -405,6 +423,7 @@ struct TsdfHooks {
     int touch_tf = -1;     // otx_touch_frames: frames per touch workgroup (-1: TF)
     int split = -1;        // otx_split_frontend: by the volume (-1), 0 never, 1 always (unsharded too)
     int defer = -1;        // otx_defer_integrate: by the volume (-1), 0 never, 1 with any split batch
+    int pretest = -1;      // otx_slice_pretest: whole volumes' full staging (-1), 0 never, 1 every batch staged in full
     bool unit_sort_radix = false;  // otx_unit_sort_radix: the radix sort at every key width
 };
 extern TsdfHooks g_tsdf_hooks;

@@ -22,11 +22,13 @@
 #include <type_traits>
 #include <utility>
 
+#include "slice_pretest.h"
 #include "tsdf.h"
 
 namespace ot {
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Raw buffer resource over [base, base + bytes): gfx9 dword3 (0x00020000, 32-bit raw data); loads past the end
 // return 0 instead of faulting.
@@ -224,14 +226,67 @@ __device__ inline bool lds_merge(unsigned long long* keys, unsigned long long* m
     return false;
 }
 
-// staging share `part` of `parts` of the pixels of frame group `grp`
+// The tile-max depth map of a frame (slice_pretest.h): eight lanes own a PRE_TILE x PRE_TILE pixel tile, one row each
+// (lane-rows i0, i0 + step, ...: i0 and step are multiples of 8 apart from the lane's own 3 bits, so a tile's eight lanes
+// run together), combine over the group and store the tile's word -- no atomics, and every word of the map is written
+// by every batch, so nothing is cleared.  The values are the staged ones (prep_depth of the same raw depth: the
+// staging's own stores may not be visible yet).  u16 depth: prep_depth is monotone in the raw value up to the
+// truncation, so the tile's largest raw value decides with one conversion unless the truncation removed it; then, and
+// for float depth or a width that is no multiple of the tile, pixel by pixel.
+// Not inlined: inside the touch kernel it took that kernel from 78 to 82 VGPRs, a wave per SIMD off its occupancy.
+__device__ inline unsigned group8_max(unsigned v) {
+    v = max(v, (unsigned)__shfl_xor((int)v, 1));
+    v = max(v, (unsigned)__shfl_xor((int)v, 2));
+    return max(v, (unsigned)__shfl_xor((int)v, 4));
+}
+__device__ __noinline__ void tile_max_range(const BatchFrame& fr, unsigned* __restrict__ map, int W, int H, int i0,
+                                            int step) {
+    const int tmx = pre_tiles(W), total = tmx * pre_tiles(H) * PRE_TILE;
+    const bool rows16 = fr.depth16 && (W & 7) == 0 && (reinterpret_cast<uintptr_t>(fr.depth16) & 15) == 0;
+    for (int i = i0; i < total; i += step) {  // (total is a multiple of 8: a group is in or out as one)
+        const int t = i >> 3, y = (t / tmx) * PRE_TILE + (i & 7), x0 = (t % tmx) * PRE_TILE;
+        const int cols = min(PRE_TILE, W - x0);
+        const bool inside = y < H;  // (a ragged tile's rows past the image hold nothing)
+        unsigned key = 0u;
+        bool done = false;  // the same for a tile's eight lanes
+        if (rows16) {  // (cols == PRE_TILE) the row is one aligned 16-B load
+            unsigned m = 0u;
+            if (inside) {
+                const uint4 v = *reinterpret_cast<const uint4*>(fr.depth16 + (int64_t)y * W + x0);
+                const unsigned w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) m = max(m, max(w4[k] & 0xFFFFu, w4[k] >> 16));
+            }
+            m = group8_max(m);
+            const float d = prep_depth(fr, m);
+            done = m == 0u || d > 0.0f;
+            key = pre_depth_key(d);
+        }
+        if (!done) {
+            key = 0u;
+            if (inside)
+                for (int c = 0; c < cols; ++c) {
+                    const int64_t px = (int64_t)y * W + x0 + c;
+                    key = max(key, pre_depth_key(fr.depth16 ? prep_depth(fr, fr.depth16[px]) : fr.depthf[px]));
+                }
+            key = group8_max(key);
+        }
+        if ((i & 7) == 0) map[t] = key;
+    }
+}
+
+// staging share `part` of `parts` of the pixels of frame group `grp`, and of the tiles of their tile-max maps
 __device__ inline void stage_share(const BatchFrame* __restrict__ frames, const BatchTouchParams& p, int nframes,
                                    int grp, int part, int parts) {
     const int64_t quads = (p.npx + 3) >> 2;
     const int64_t per = (quads + parts - 1) / parts;
     const int64_t q0 = (int64_t)part * per, q1 = q0 + per < quads ? q0 + per : quads;
-    for (int f = grp * p.tf; f < grp * p.tf + p.tf && f < nframes; ++f)
+    for (int f = grp * p.tf; f < grp * p.tf + p.tf && f < nframes; ++f) {
         prep_range(frames[f], q0 + threadIdx.x, q1, p.npx);
+        if (p.tmax)
+            tile_max_range(frames[f], p.tmax + (size_t)f * (pre_tiles(p.W) * pre_tiles(p.H)), p.W, p.H,
+                           part * 256 + (int)threadIdx.x, parts * 256);
+    }
 }
 
 // Staging (every pixel of the batch: HBM streaming) and the touch (stride samples: LDS merges and global hash atomics)
@@ -973,16 +1028,51 @@ __device__ __forceinline__ void integrate_frames(const BatchFrame* __restrict__ 
     }
 }
 
+// The slice pre-test (slice_pretest.h), in the coarse item's prologue: lane f decides frame f of the item's mask from
+// the slice's bounding box in that frame's image and the frame's tile-max depth map -- the map read through a buffer
+// resource over the whole set's maps, so a wrong index reads 0 or another tile and cannot fault -- and the ballot is the
+// frames in which no voxel of the slice can be a candidate.  Such a frame is one integrate_frames leaves at its idle
+// branch with every lane selecting the old value: dropping its bit changes no voxel, no update count and no write-back
+// decision.  Float64 and per-lane loops are fine here: once per item, before the voxel state is loaded.
+__device__ __forceinline__ unsigned long long pretest_idle(const BatchFrame* __restrict__ frames,
+                                                           const IntegrateParams& p, const UnitWork& w, int s,
+                                                           unsigned long long mask) {
+    // per-item copies of the lane index and the launch's constants: what derives from them alone (the frame's address,
+    // float64 forms and products) would otherwise be computed before the item loop and kept through the frame loop,
+    // which has no register to spare (they were spilled)
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int f = (int)(tid & 63u);
+    bool idle = false;
+    PreIntrinsics in;
+    in.W = p.W, in.H = p.H, in.fx = p.fx, in.fy = p.fy, in.cx = p.cx, in.cy = p.cy;
+    float vl = p.vl, trunc = p.trunc;
+    double unit_len = p.unit_len;
+    asm volatile("" : "+s"(in.fx), "+s"(in.fy), "+s"(in.cx), "+s"(in.cy), "+s"(vl), "+s"(trunc), "+s"(unit_len));
+    asm volatile("" : "+s"(in.W), "+s"(in.H));
+    if ((mask >> f) & 1ull) {
+        const __amdgpu_buffer_rsrc_t map = make_rsrc(p.tmax, (p.tmax_words + PRE_SLACK) * 4);
+        const int base = f * p.tmax_tiles;
+        idle = slice_idle(frames[f].E, in, vl, unit_len, w.kx, w.ky, w.kz, s, trunc, [&](int i) {
+            // (PRE_NONE: 2^30 bytes or more into a buffer of fewer: the range check answers zeros)
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(map, (base + i) * 4, 0, 0);
+            PreTile4 q;
+            q.k[0] = v.x, q.k[1] = v.y, q.k[2] = v.z, q.k[3] = v.w;
+            return q;
+        });
+    }
+    return __builtin_amdgcn_ballot_w64(idle);
+}
+
 // One work item: slice s (this wave's) of the unit of work entry w -- its ZB voxels per lane loaded (or zero for a
-// fresh unit), taken through the batch's frames of w.mask and written back.  ZB == 2: the fine slices (KT their
-// pipeline's depth).
+// fresh unit), taken through the batch's frames of `mask` (w.mask, less the frames the pre-test dropped) and written
+// back.  ZB == 2: the fine slices (KT their pipeline's depth).
 template <bool C64, bool FAST, int ZB, int KT>
 __device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ frames, const IntegrateParams& p,
-                                               const TsdfDev& d, const UnitWork& w, int s, int npx,
-                                               const float* s_r32, const double* s_r64, unsigned& upd) {
+                                               const TsdfDev& d, const UnitWork& w, unsigned long long mask, int s,
+                                               int npx, const float* s_r32, const double* s_r64, unsigned& upd) {
     using CT = typename std::conditional<C64, double, float>::type;
     const int ent = w.id;
-    const unsigned long long mask = w.mask;
     if (ent == -1) return;
     const int id = ent & 0x7FFFFFFF;
     const bool fresh = ent < 0;
@@ -1152,7 +1242,8 @@ struct RcpLds {
 // The grid is sized for large batches (8x the resident workgroups): a workgroup without an item leaves before
 // building the reciprocal table -- for a batch of few units (a spatial shard) the idle workgroups' tables had cost
 // more than the integrate itself (r05e: a 1/8 shard's 64-frame batch 165-200 us whatever its slicing)
-template <bool C64, bool FAST, int ZB, int KT, bool HEAVY, int WG>
+// PRE: the launch of its own with coarse slices runs the slice pre-test when the batch has tile-max maps (p.tmax).
+template <bool C64, bool FAST, int ZB, int KT, bool HEAVY, int WG, bool PRE = false>
 __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ frames, const IntegrateParams& p,
                                                const TsdfDev& d, const UnitWork* __restrict__ work,
                                                const int* __restrict__ wcount, float* s_r32, double* s_r64, int bid,
@@ -1176,17 +1267,32 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
     const int nh = HEAVY ? wcount[2] : 0;  // heavy units first; the rest are stored back to front (k_batch_units)
     const int npx = p.W * p.H;
     unsigned upd = 0;  // per lane: <= ZB voxels x 64 frames x units per workgroup, far below 2^32
+    unsigned dropped = 0;  // wave-uniform: wave-frames the pre-test dropped
     const int items = PARTS == 1 ? n : ((n + 7) / 8) * 8 * PARTS;
     for (int it = bid; it < items; it += nblk) {
         const int u = PARTS == 1 ? it : (it / (8 * PARTS)) * 8 + (it & 7);
         if (PARTS > 1 && u >= n) continue;
         const int part = PARTS == 1 ? 0 : (it >> 3) % PARTS;
         const int s = part * WG + wave;  // slice of this wave
-        integrate_item<C64, FAST, ZB, KT>(frames, p, d, work[!HEAVY || u < nh ? u : n - 1 - (u - nh)], s, npx, s_r32,
-                                          s_r64, upd);
+        const UnitWork& w = work[!HEAVY || u < nh ? u : n - 1 - (u - nh)];
+        unsigned long long mask = w.mask;
+        if constexpr (PRE) {
+            if (p.tmax && w.id != -1) {  // wave-uniform
+                const unsigned long long idle = pretest_idle(frames, p, w, s, mask);
+                mask &= ~idle;
+                dropped += (unsigned)__popcll(idle);
+                if (!mask && w.id >= 0) continue;  // (a fresh unit still writes its zeros)
+            }
+        }
+        integrate_item<C64, FAST, ZB, KT>(frames, p, d, w, mask, s, npx, s_r32, s_r64, upd);
     }
     const unsigned long long tot = wave_sum((unsigned long long)upd);
-    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(&d.stats[S_UPDATES], tot);
+    if ((threadIdx.x & 63) == 0 && tot)
+        atomicAdd(&d.stats[S_UPD_BASE + (bid & (S_DROP_LINES - 1)) * S_DROP_STRIDE], tot);
+    if constexpr (PRE) {
+        if ((threadIdx.x & 63) == 0 && dropped)
+            atomicAdd(&d.stats[S_DROP_BASE + (bid & (S_DROP_LINES - 1)) * S_DROP_STRIDE], (unsigned long long)dropped);
+    }
 }
 
 // the integrate of a batch as a launch of its own (the product kernel: <C64, FAST, BZ, 1, 1>; ZB == 2: fine slices).
@@ -1197,8 +1303,9 @@ template <bool C64, bool FAST, int ZB = BZ, int KT = 1, int WG = INT_WG>
 __global__ __launch_bounds__(64 * WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : INT_WAVES_PER_EU)) void k_batch_integrate(
     const BatchFrame* __restrict__ frames, IntegrateParams p, TsdfDev d, const UnitWork* __restrict__ work,
     const int* __restrict__ wcount) {
-    integrate_body<C64, FAST, ZB, KT, false, WG>(frames, p, d, work, wcount, reinterpret_cast<float*>(s_rcp_dyn),
-                                                 s_rcp_dyn, (int)blockIdx.x, (int)gridDim.x);
+    integrate_body<C64, FAST, ZB, KT, false, WG, ZB == BZ>(frames, p, d, work, wcount,
+                                                           reinterpret_cast<float*>(s_rcp_dyn), s_rcp_dyn,
+                                                           (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The deferred integrate of a sharded volume's batch k and the touch of batch k + 1 in ONE launch (round 6): workgroups
@@ -1281,6 +1388,8 @@ static IntegrateParams make_integrate_params(const ot_tsdf* vol, const float* de
     p.proj_eps = (float)(std::ldexp((double)std::max(in->width, in->height) + 2.0, -21) + 1.2e-4);
     p.rcp_hi = RCP_N;  // (integrate_batch narrows it to the batch)
     p.unit_len = vol->unit_length;
+    p.tmax = nullptr;  // (integrate_batch: the batch's maps, when its plan has the pre-test)
+    p.tmax_tiles = p.tmax_words = 0;
     return p;
 }
 
@@ -1622,6 +1731,11 @@ static ot_status grow_pool(ot_tsdf* vol, int64_t need, int n_used, hipStream_t s
 // and where its work list's length lives.  Nothing after this asks the volume or the hooks for the mode again.
 static ot_status plan_batch(ot_tsdf* vol, const ot_intrinsics& in, int pc, BatchPlan& p) {
     p.split = split_on(vol) && tmask_fits(in.width, in.height);
+    // the slice pre-test needs every pixel of every frame staged, with its tile-max map: not the split front end's
+    // marked tiles.  Default: whole volumes (a shard's few units per batch take the fused launches or the fine slices)
+    const int pre = g_tsdf_hooks.pretest;
+    p.pretest = !p.split && (pre > 0 || (pre < 0 && vol->dev.shard_world <= 1)) &&
+                (int64_t)pre_tiles(in.width) * pre_tiles(in.height) * MAX_BATCH + PRE_SLACK < (int64_t)PRE_NONE;
     p.mode = defer_on(vol, p.split) ? BatchMode::Deferred : overlap_on(vol) ? BatchMode::Overlap : BatchMode::Direct;
     p.wcount = vol->dev.counters + pc;
     if (p.mode != BatchMode::Direct) {  // the sets alternate; each has its own copy of the count
@@ -1673,6 +1787,8 @@ static BatchTouchParams make_touch_params(const ot_tsdf* vol, const ot_intrinsic
     // sharded volume: split front end (touch without staging -> units -> tile mask -> staging of the marked tiles)
     tp.sample_stage = split ? 1 : 0;
     if (split) tp.stage_blocks = -1;
+    tp.tmax = nullptr;  // (integrate_batch: the set's maps, when the batch's plan has the pre-test)
+    tp.H = in.height;
     return tp;
 }
 
@@ -1885,6 +2001,24 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
     hipLaunchKernelGGL(k_copy_frames, dim3(1), dim3(COPY_FRAMES_LANES), 0, stream, (const uint4*)host,
                        (uint4*)bs.bframes, (int)(sizeof(BatchFrame) / 16) * n);
     bc.tp = make_touch_params(vol, in, bc.pc, plan.split);
+    if (plan.pretest) {  // the set's tile-max maps: written by this batch's staging, read by its integrate and a replay's
+        const int64_t tiles = (int64_t)pre_tiles(in.width) * pre_tiles(in.height);
+        if (bs.tmax_cap < tiles * n) {
+            if (bs.tmax) {
+                OT_HIP_TRY(hipStreamSynchronize(stream));
+                if (vol->istream) OT_HIP_TRY(hipStreamSynchronize(vol->istream));
+                OT_HIP_TRY(hipFree(bs.tmax));
+                bs.tmax = nullptr, bs.tmax_cap = 0;
+            }
+            const int64_t cap = tiles * std::max(n, std::min(vol->batch_max, MAX_BATCH));
+            OT_HIP_TRY(hipMalloc(&bs.tmax, sizeof(unsigned) * (cap + PRE_SLACK)));
+            bs.tmax_cap = cap;
+        }
+        bc.tp.tmax = bs.tmax;
+        bc.ip0.tmax = bs.tmax;
+        bc.ip0.tmax_tiles = (int)tiles;
+        bc.ip0.tmax_words = (int)(tiles * n);
+    }
     if (plan.split) {
         if ((st = ensure_tmask(vol, in.width, in.height, stream)) != OT_OK) return st;
         bc.sq = make_stage_params(vol, in, bc.ip0, n);

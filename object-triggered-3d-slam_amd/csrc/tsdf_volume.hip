@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void k_tsdf_clear(TsdfDev d, int64_t cap) {
     }
     if (blockIdx.x == 0) {
         if (threadIdx.x < N_COUNTERS) d.counters[threadIdx.x] = 0;
-        if (threadIdx.x < 4) d.stats[threadIdx.x] = 0ull;
+        for (int i = threadIdx.x; i < N_STATS; i += 256) d.stats[i] = 0ull;
     }
 }
 
@@ -139,7 +139,7 @@ ot_status ot_tsdf_create(double voxel_length, double sdf_trunc, int32_t color_ty
     if ((e = hipMalloc(&d.hkeys, sizeof(unsigned long long) * cap)) != hipSuccess) return cleanup(e);
     if ((e = hipMalloc(&d.hvals, sizeof(int) * cap)) != hipSuccess) return cleanup(e);
     if ((e = hipMalloc(&d.counters, sizeof(int) * N_COUNTERS)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.stats, sizeof(unsigned long long) * 4)) != hipSuccess) return cleanup(e);
+    if ((e = hipMalloc(&d.stats, sizeof(unsigned long long) * N_STATS)) != hipSuccess) return cleanup(e);
     if ((e = hipMalloc(&d.unit_keys, sizeof(int) * 3 * max_units)) != hipSuccess) return cleanup(e);
     // RGB8 volumes keep colour at Open3D's precision (float64, 128-KiB records) unless set_color_precision(32)
     v->color64 = color_type == OT_COLOR_RGB8;
@@ -175,7 +175,7 @@ ot_status ot_tsdf_destroy(ot_tsdf* v) {
     void* ptrs[] = {d.hkeys, d.hvals, d.counters, d.stats, d.unit_keys, d.vox, v->mult, v->sorted_ids, v->mesh.ws,
                     v->mesh.v, v->mesh.c, v->mesh.t, v->mesh.vk, v->mesh.tk, v->mesh.vown, d.fmask, d.bslots, d.work,
                     v->cloud.ws, v->wcount, v->bset[0].bframes, v->bset[0].bdc, v->bset[1].bframes, v->bset[1].bdc,
-                    v->bset[1].work, v->tmask};
+                    v->bset[1].work, v->tmask, v->bset[0].tmax, v->bset[1].tmax};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (v->hbframes) (void)hipHostFree(v->hbframes);
@@ -205,7 +205,7 @@ ot_status ot_tsdf_reset(ot_tsdf* v) {
     OT_HIP_TRY(hipMemset(d.hvals, 0xFF, sizeof(int) * v->hash_cap));
     OT_HIP_TRY(hipMemset(d.fmask, 0, sizeof(unsigned long long) * v->hash_cap));
     OT_HIP_TRY(hipMemset(d.counters, 0, sizeof(int) * N_COUNTERS));
-    OT_HIP_TRY(hipMemset(d.stats, 0, sizeof(unsigned long long) * 4));
+    OT_HIP_TRY(hipMemset(d.stats, 0, sizeof(unsigned long long) * N_STATS));
     OT_HIP_TRY(hipDeviceSynchronize());
     v->pending.clear();
     v->dfr_on = false;  // a deferred batch's integrate belongs to the old contents (its work list is stale now)
@@ -284,9 +284,11 @@ ot_status ot_tsdf_counters(ot_tsdf* vol, int64_t* updates, int64_t* unit_integra
     hipStream_t stream = S(stream_);
     ot_status st = tsdf_flush(vol, stream);
     if (st != OT_OK) return st;
-    unsigned long long s[4];
-    OT_HIP_TRY(hipMemcpyAsync(s, vol->dev.stats, sizeof(s), hipMemcpyDeviceToHost, stream));
+    std::vector<unsigned long long> s(N_STATS);
+    OT_HIP_TRY(hipMemcpyAsync(s.data(), vol->dev.stats, sizeof(unsigned long long) * N_STATS, hipMemcpyDeviceToHost,
+                              stream));
     OT_HIP_TRY(hipStreamSynchronize(stream));
+    for (int i = 0; i < S_DROP_LINES; ++i) s[S_UPDATES] += s[S_UPD_BASE + i * S_DROP_STRIDE];
     if (updates) *updates = (int64_t)s[S_UPDATES];
     if (unit_integrations) *unit_integrations = (int64_t)s[S_UNIT_INTEGRATIONS];
     return OT_OK;
@@ -373,12 +375,18 @@ ot_status ot_tsdf_frontend_time(ot_tsdf* vol, double* total_ms, int64_t* batches
 }
 
 // test / diagnostic hook (not part of the drop-in boundary): the volume's raw u64 stats[4] (0 voxel updates,
-// 1 unit integrations; 2, 3 unused)
+// 1 unit integrations, 2 wave-frames the slice pre-test dropped since reset; 3 unused)
 ot_status otx_tsdf_stats(ot_tsdf* vol, uint64_t* out4) {
     if (!vol || !out4) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
     ot_status st = tsdf_flush(vol, nullptr);
     if (st != OT_OK) return st;
-    OT_HIP_TRY(hipMemcpy(out4, vol->dev.stats, sizeof(uint64_t) * 4, hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> s(N_STATS);
+    OT_HIP_TRY(hipMemcpy(s.data(), vol->dev.stats, sizeof(unsigned long long) * N_STATS, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) out4[i] = s[i];
+    for (int i = 0; i < S_DROP_LINES; ++i) {
+        out4[S_PRETEST_DROPPED] += s[S_DROP_BASE + i * S_DROP_STRIDE];
+        out4[S_UPDATES] += s[S_UPD_BASE + i * S_DROP_STRIDE];
+    }
     return OT_OK;
 }
 
@@ -460,6 +468,14 @@ ot_status otx_integrate_depth(int32_t kt) {
 ot_status otx_defer_integrate(int32_t mode) {
     if (mode < -1 || mode > 1) return fail(OT_ERR_INVALID_ARGUMENT, "deferred integrate mode must be -1, 0 or 1");
     g_tsdf_hooks.defer = mode;
+    return OT_OK;
+}
+
+// test hook: the coarse integrate's slice pre-test (-1 = whole volumes' batches staged in full, the default; 0 = never;
+// 1 = every batch staged in full, a sharded volume's too): A/B timing and the parity of both forms
+ot_status otx_slice_pretest(int32_t mode) {
+    if (mode < -1 || mode > 1) return fail(OT_ERR_INVALID_ARGUMENT, "slice pre-test mode must be -1, 0 or 1");
+    g_tsdf_hooks.pretest = mode;
     return OT_OK;
 }
 
