@@ -171,6 +171,8 @@ TEST_SIGNATURES = {
     "otx_touch_frames": [_i32],
     "otx_split_frontend": [_i32],
     "otx_slice_pretest": [_i32],
+    "otx_stage_onepass": [_i32],
+    "otx_tsdf_staged": [_p, _i32, _p, _p],
     "otx_defer_integrate": [_i32],
     "otx_integrate_depth": [_i32],
     "otx_mc_emit_fork": [_i32],

@@ -232,6 +232,8 @@ struct BatchTouchParams {
                         // (a replay touch reads it; k_stage_tiles stages only the owned units' footprints)
     unsigned* tmax;     // the set's tile-max depth maps, written by the staging (frame f's at tmax + f * tiles); nullptr: none
     int H;
+    int onepass;        // eligible frames are staged in 8 x 8 tile order and their map words reduced from the depths in
+                        // registers (tsdf.hip stage_tile_quads); 0: every frame by pixel chunks, the map from a second read
 };
 
 // parameters of the split front end's tile-mask kernel (tsdf.hip make_stage_params)
@@ -383,6 +385,9 @@ struct ot_tsdf {
     int64_t stat_batches = 0, stat_unit_batches = 0, stat_fresh = 0, stat_prev_units = 0;
     int64_t last_batch_slots = -1;  // units the last batch touched (mailed): the next batch's integrate granularity
     int bset_next = 0;            // set of the next batch (alternates in overlap mode)
+    // the last batch's staging (otx_tsdf_staged): its set, frames, image size and whether it wrote tile-max maps
+    int staged_set = -1, staged_n = 0, staged_w = 0, staged_h = 0;
+    bool staged_map = false;
     int last_set = -1;            // set of the last batch whose integrate ran on istream (joined by readers)
     hipStream_t istream = nullptr;
     int* wcount = nullptr;        // device [2]: the sets' work-list lengths (k_batch_units -> k_batch_integrate)
@@ -424,6 +429,7 @@ struct TsdfHooks {
     int split = -1;        // otx_split_frontend: by the volume (-1), 0 never, 1 always (unsharded too)
     int defer = -1;        // otx_defer_integrate: by the volume (-1), 0 never, 1 with any split batch
     int pretest = -1;      // otx_slice_pretest: whole volumes' full staging (-1), 0 never, 1 every batch staged in full
+    int onepass = -1;      // otx_stage_onepass: staging and tile-max map in one pass where eligible (-1), 0 never
     bool unit_sort_radix = false;  // otx_unit_sort_radix: the radix sort at every key width
 };
 extern TsdfHooks g_tsdf_hooks;

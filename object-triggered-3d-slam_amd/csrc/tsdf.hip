@@ -64,12 +64,13 @@ __device__ inline void st_f64(__amdgpu_buffer_rsrc_t r, int i, double x) {
 // multiplier depends on the pixel and the intrinsics alone: it is not staged per frame, the integrate gathers it from
 // the volume's one table (vol->mult, IntegrateParams::mult), and only on the lanes that can update.
 // depth: u16 path converted exactly as Image::ConvertDepthToFloatImage; float path copied.
-__device__ inline float prep_depth(const BatchFrame& fr, uint32_t raw16) {
+__device__ inline float prep_depth(float scale, double trunc, uint32_t raw16) {
     float dv = (float)raw16;
-    dv = dv / fr.scale;
-    if ((double)dv >= fr.trunc) dv = 0.0f;
+    dv = dv / scale;
+    if ((double)dv >= trunc) dv = 0.0f;
     return dv;
 }
+__device__ inline float prep_depth(const BatchFrame& fr, uint32_t raw16) { return prep_depth(fr.scale, fr.trunc, raw16); }
 
 // the staged records of 4 consecutive pixels (depths d, the 12 colour bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3 as
 // three words; zeros without colour): two 16-B stores
@@ -275,6 +276,77 @@ __device__ __noinline__ void tile_max_range(const BatchFrame& fr, unsigned* __re
     }
 }
 
+// Staging and map in one pass (u16 depth in 16-B aligned rows of whole tiles, colour absent or 4-B aligned:
+// stage_onepass): the frame is staged in tile order and a tile's word is the largest pre_depth_key of the CONVERTED
+// depths its lanes hold, so the raw depth is read once and the truncation needs no second look.  A wave takes a strip of
+// eight consecutive tiles, 16 quads wide and 8 rows high, a lane two quads of it: lane-quad i has bits 0..3 the quad of
+// the row (bit 0 the half of the tile), bits 4..5 the row r, the rest the strip, and the lane stages rows r and r + 4 --
+// per row as prep_quad does (8-B depth load, 12 B of colour, two 16-B stores), both rows' loads issued before the first
+// store.  Sixteen adjacent lanes read 128 B of depth and 192 B of colour and write 512 B of one image row, the
+// pattern of the chunked staging (a lane per tile row, 16 B of depth and four 16-B stores 64 B apart, was 12 us per
+// batch slower: DESIGN.md 4.3).  A tile's eight lanes (1, 16 and 32 apart) share a wave: i0 and step are multiples of
+// 64 apart from the lane's own 6 bits, and the strips' lane-quads in all a multiple of 64.  Rows past H are not stored
+// and count 0, and neither are the tiles past the frame's last (a last strip of fewer than eight); their lanes load the
+// nearest row or tile inside instead, so the loads stay straight-line code.  The accesses are global_, not flat_: the
+// pointers come out of BatchFrame in memory with no address space, and a flat access also waits on the LDS counter.
+// Not inlined, as tile_max_range: inside the touch kernel it took that kernel from 79 to 86 VGPRs.
+typedef const uint32_t __attribute__((address_space(1))) * gc_u32;
+typedef u32x4 __attribute__((address_space(1))) * g_u32x4;
+typedef unsigned __attribute__((address_space(1))) * g_u32;
+__device__ inline bool stage_onepass(const BatchFrame& fr, int W) {
+    return fr.depth16 && (reinterpret_cast<uintptr_t>(fr.depth16) & 15) == 0 && (W & 7) == 0 &&
+           (reinterpret_cast<uintptr_t>(fr.color) & 3) == 0;
+}
+typedef const u32x2 __attribute__((address_space(1))) * gc_u32x2;
+__device__ __noinline__ void stage_tile_quads(const BatchFrame& fr, unsigned* map, int W, int H, int i0, int step) {
+    const int tmx = W >> 3, ntiles = tmx * pre_tiles(H), total = ((ntiles + 7) >> 3) * 64;
+    const BatchFrame __attribute__((address_space(1)))* g = (const BatchFrame __attribute__((address_space(1)))*)&fr;
+    const uint16_t* depth = g->depth16;
+    const uint8_t* color = g->color;
+    uint2* dc = g->dc;
+    const float scale = g->scale;  // (read once: the stores below may alias the frame's parameters)
+    const double trunc = g->trunc;
+    for (int i = i0; i < total; i += step) {  // (a wave is in or out as one)
+        const int c = i & 15, t = (i >> 6) * 8 + (c >> 1), tc = min(t, ntiles - 1);
+        const int ty = tc / tmx, y = ty * PRE_TILE + ((i >> 4) & 3), x = (tc - ty * tmx) * PRE_TILE + (c & 1) * 4;
+        const int rows = t < ntiles ? (y + 4 < H ? 2 : y < H ? 1 : 0) : 0;  // of the lane's two, those inside the image
+        // every lane loads (a row past the image or a tile past the last: the nearest one inside, and nothing stored),
+        // so the loads are straight-line code, all in flight before the first store
+        int64_t px[2];
+        u32x2 raw[2];
+        uint32_t w[2][3] = {{0u, 0u, 0u}, {0u, 0u, 0u}};  // colour loaded before the stores (char data may alias them)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            px[k] = (int64_t)min(y + 4 * k, H - 1) * W + x;
+            raw[k] = *(gc_u32x2)(depth + px[k]);
+        }
+        if (color) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                gc_u32 cw = (gc_u32)(color + px[k] * 3);  // 12 B, 4-B aligned
+                w[k][0] = cw[0], w[k][1] = cw[1], w[k][2] = cw[2];
+            }
+        }
+        unsigned key = 0u;
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (k < rows) {  // as store_quad
+                const float d0 = prep_depth(scale, trunc, raw[k].x & 0xFFFFu), d1 = prep_depth(scale, trunc, raw[k].x >> 16);
+                const float d2 = prep_depth(scale, trunc, raw[k].y & 0xFFFFu), d3 = prep_depth(scale, trunc, raw[k].y >> 16);
+                const uint32_t w0 = w[k][0], w1 = w[k][1], w2 = w[k][2];
+                g_u32x4 out = (g_u32x4)(dc + px[k]);
+                out[0] = u32x4{__float_as_uint(d0), w0 & 0xFFFFFFu, __float_as_uint(d1), (w0 >> 24) | ((w1 & 0xFFFFu) << 8)};
+                out[1] = u32x4{__float_as_uint(d2), (w1 >> 16) | ((w2 & 0xFFu) << 16), __float_as_uint(d3), w2 >> 8};
+                key = max(max(key, max(pre_depth_key(d0), pre_depth_key(d1))),
+                          max(pre_depth_key(d2), pre_depth_key(d3)));
+            }
+        key = max(key, (unsigned)__shfl_xor((int)key, 1));
+        key = max(key, (unsigned)__shfl_xor((int)key, 16));
+        key = max(key, (unsigned)__shfl_xor((int)key, 32));
+        if ((i & 0x31) == 0 && t < ntiles) *(g_u32)(map + t) = key;
+    }
+}
+
 // staging share `part` of `parts` of the pixels of frame group `grp`, and of the tiles of their tile-max maps
 __device__ inline void stage_share(const BatchFrame* __restrict__ frames, const BatchTouchParams& p, int nframes,
                                    int grp, int part, int parts) {
@@ -282,6 +354,11 @@ __device__ inline void stage_share(const BatchFrame* __restrict__ frames, const 
     const int64_t per = (quads + parts - 1) / parts;
     const int64_t q0 = (int64_t)part * per, q1 = q0 + per < quads ? q0 + per : quads;
     for (int f = grp * p.tf; f < grp * p.tf + p.tf && f < nframes; ++f) {
+        if (p.tmax && p.onepass && stage_onepass(frames[f], p.W)) {  // workgroup-uniform
+            unsigned* map = p.tmax + (size_t)f * (pre_tiles(p.W) * pre_tiles(p.H));
+            stage_tile_quads(frames[f], map, p.W, p.H, part * 256 + (int)threadIdx.x, parts * 256);
+            continue;
+        }
         prep_range(frames[f], q0 + threadIdx.x, q1, p.npx);
         if (p.tmax)
             tile_max_range(frames[f], p.tmax + (size_t)f * (pre_tiles(p.W) * pre_tiles(p.H)), p.W, p.H,
@@ -1789,6 +1866,7 @@ static BatchTouchParams make_touch_params(const ot_tsdf* vol, const ot_intrinsic
     if (split) tp.stage_blocks = -1;
     tp.tmax = nullptr;  // (integrate_batch: the set's maps, when the batch's plan has the pre-test)
     tp.H = in.height;
+    tp.onepass = g_tsdf_hooks.onepass != 0;
     return tp;
 }
 
@@ -2015,6 +2093,10 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
             bs.tmax_cap = cap;
         }
         bc.tp.tmax = bs.tmax;
+        // one-pass staging (stage_tile_quads): a wave per strip of eight tiles and frame, so no staging workgroup idles
+        // (640 x 480: 150 workgroups per frame group instead of 160, front end 82.8 -> 79.4 us per batch; 80: 83.1)
+        if (bc.tp.onepass && g_tsdf_hooks.stage_blocks < 0 && bc.tp.stage_blocks > 0 && in.width % PRE_TILE == 0)
+            bc.tp.stage_blocks = (int)((tiles + 31) / 32);
         bc.ip0.tmax = bs.tmax;
         bc.ip0.tmax_tiles = (int)tiles;
         bc.ip0.tmax_words = (int)(tiles * n);
@@ -2064,6 +2146,8 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
         }
     }
     vol->batch_pc ^= 1;  // only once this batch's kernels are queued (its units kernel zeroes the other counter)
+    vol->staged_set = plan.set, vol->staged_n = n, vol->staged_w = in.width, vol->staged_h = in.height;
+    vol->staged_map = bc.tp.tmax != nullptr;
     vol->frame_id += n;
     vol->sorted_frame = -1;
     vol->early_frame = vol->frame_id;  // the mailed counters are final for this frame count (see units_seq)

@@ -8,6 +8,7 @@
 #include <sched.h>
 #include <thread>
 
+#include "slice_pretest.h"
 #include "tsdf.h"
 
 namespace ot {
@@ -476,6 +477,36 @@ ot_status otx_defer_integrate(int32_t mode) {
 ot_status otx_slice_pretest(int32_t mode) {
     if (mode < -1 || mode > 1) return fail(OT_ERR_INVALID_ARGUMENT, "slice pre-test mode must be -1, 0 or 1");
     g_tsdf_hooks.pretest = mode;
+    return OT_OK;
+}
+
+// test hook: the staging's one-pass form (-1 = the default: an eligible frame of a batch with tile-max maps is staged
+// in tile order and its map reduced from the depths in registers; 0 = every frame by pixel chunks and the map from a
+// second read of the raw depth): A/B timing and the parity of both forms
+ot_status otx_stage_onepass(int32_t mode) {
+    if (mode < -1 || mode > 0) return fail(OT_ERR_INVALID_ARGUMENT, "one-pass staging mode must be -1 or 0");
+    g_tsdf_hooks.onepass = mode;
+    return OT_OK;
+}
+
+// test / diagnostic hook: frame `frame` of the last batch's staging set as the staging left it -- its W x H 8-B records
+// (float depth bits, colour word) to records_out and, unless map_out is null, the pre_tiles(W) x pre_tiles(H) words of
+// its tile-max map (host memory both).  An error if that batch built no map and one is asked for.
+ot_status otx_tsdf_staged(ot_tsdf* vol, int32_t frame, uint64_t* records_out, uint32_t* map_out) {
+    if (!vol || !records_out) return fail(OT_ERR_INVALID_ARGUMENT, "invalid arguments");
+    ot_status st = tsdf_flush(vol, nullptr);
+    if (st != OT_OK) return st;
+    if (vol->staged_set < 0 || frame < 0 || frame >= vol->staged_n)
+        return fail(OT_ERR_INVALID_ARGUMENT, "otx_tsdf_staged: no such frame in the last batch");
+    if (map_out && !vol->staged_map) return fail(OT_ERR_INVALID_ARGUMENT, "otx_tsdf_staged: the last batch built no map");
+    OT_HIP_TRY(hipDeviceSynchronize());
+    const auto& bs = vol->bset[vol->staged_set];
+    const int64_t npx = (int64_t)vol->staged_w * vol->staged_h;
+    OT_HIP_TRY(hipMemcpy(records_out, bs.bdc + npx * frame, sizeof(uint2) * npx, hipMemcpyDeviceToHost));
+    if (map_out) {
+        const int64_t tiles = (int64_t)pre_tiles(vol->staged_w) * pre_tiles(vol->staged_h);
+        OT_HIP_TRY(hipMemcpy(map_out, bs.tmax + tiles * frame, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
+    }
     return OT_OK;
 }
 
