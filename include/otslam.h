@@ -109,6 +109,23 @@ ot_status ot_cluster_dbscan(const double* xyz, int64_t n, double eps, int32_t mi
                             int32_t* out_labels /* device [n], input order */,
                             int32_t* n_clusters_host, void* stream);
 
+/* geometry.PointCloud.segment_plane(distance_threshold, ransac_n, num_iterations, probability, seed) — Open3D's
+ * PointCloud::SegmentPlane with a seeded sampler ("Plane segmentation", holds the whole definition).
+ * Iteration it keeps the first ransac_n distinct indices among z(seed, (it << 32) + t) mod n, t = 0, 1, ... (z: the
+ * counter RNG of the mesh sampler), fits their plane (3 points: the triangle's plane; more: GetPlaneFromPoints), and
+ * counts the points with |((a x + b y) + c z) + d| < distance_threshold (strict).  Open3D's serial loop is replayed on
+ * those counts: a zero plane is skipped without counting, the best candidate is the one of highest count and, among
+ * equal counts, smallest inlier_rmse = (serial sum of the inlier distances) / sqrt(k), the earliest among equal ones;
+ * the loop stops once the iterations counted exceed trunc(log(1 - probability) / log(1 - fitness^ransac_n)).
+ * inliers: the best plane's inlier indices ascending (device int64, capacity n); plane_host: GetPlaneFromPoints over
+ * them (a, b, c, d; the zero plane when there are none); *evaluated_host (nullable): iterations counted.  All float64,
+ * no contraction; two calls give the same bits.  Errors (OT_ERR_INVALID_ARGUMENT, before any device work, in this
+ * order): probability outside (0, 1], ransac_n < 3, n < ransac_n; ransac_n > 32 is not supported by this build. */
+ot_status ot_segment_plane(const double* xyz, int64_t n, double distance_threshold, int32_t ransac_n,
+                           int32_t num_iterations, double probability, uint64_t seed, double plane_host[4],
+                           int64_t* inliers /* device int64, capacity n */, int64_t* n_inliers_host,
+                           int32_t* evaluated_host /* iterations counted */, void* stream);
+
 /* geometry.PointCloud.estimate_covariances(search_param) — Open3D's EstimatePerPointCovariances (DESIGN.md §4,
  * "normals").  Neighbours of point i: every point j of the cloud (i included) ordered ascending by (d2, j) with
  * d2 = ((dx dx) + dy dy) + dz dz in float64; the first min(knn, n) of them, and with radius > 0 (hybrid search) only

@@ -56,6 +56,7 @@ SIGNATURES = {
     "ot_remove_statistical_outlier": [_p, _i64, _i32, _d, _p, _p, _pi64, _p],
     "ot_remove_radius_outlier": [_p, _i64, _i32, _d, _p, _pi64, _p],
     "ot_cluster_dbscan": [_p, _i64, _d, _i32, _p, C.POINTER(C.c_int32), _p],
+    "ot_segment_plane": [_p, _i64, _d, _i32, _i32, _d, C.c_uint64, _p, _p, _pi64, C.POINTER(C.c_int32), _p],
     "ot_estimate_covariances": [_p, _i64, _i32, _d, _p, _p],
     "ot_estimate_normals": [_p, _i64, _i32, _d, _p, _p, _p, _p],
     "ot_orient_normals": [_p, _p, _i64, _i32, _pd, _p],
@@ -182,6 +183,8 @@ TEST_SIGNATURES = {
     "otx_sort_segments_u32_u32": [_p, _p, _p, _p, _p, _i32, _i32, _p],
     "otx_alloc_count": [],
     "otx_registration_last_d2": [_p, _i64, _p],
+    "otx_segment_plane_chunk": [_i32],
+    "otx_segment_plane_profile": [_i32, _pd],
 }
 
 

@@ -18,6 +18,7 @@
 #include "chain.h"
 #include "compact.h"
 #include "mesh_area.h"
+#include "rng.h"
 #include "sort.h"
 
 namespace ot {
@@ -759,14 +760,6 @@ __global__ __launch_bounds__(256) void k_round_counts(const double* __restrict__
     if (t >= nt) return;
     long long v = (long long)round(cdf[t] * (double)N);
     ncum[t] = v < N ? v : N;
-}
-
-__device__ inline double rng_u01(unsigned long long seed, unsigned long long ctr) {
-    unsigned long long z = seed + (ctr + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
 }
 
 // barycentric weights of point k from the counter RNG

@@ -571,6 +571,30 @@ class PointCloud:
                C.byref(k), D.stream_ptr())
         return IntVector(D.to_host(labels).tolist())
 
+    def segment_plane(self, distance_threshold, ransac_n=3, num_iterations=100, probability=0.99999999, seed=0):
+        """PointCloud::SegmentPlane — ot_segment_plane (DESIGN.md §4 "Plane segmentation").  Returns (plane_model,
+        inliers): the plane a x + b y + c z + d = 0 refitted to the best candidate's inliers as a float64 array of
+        shape (4,), and the inlier indices ascending as an IntVector (select_by_index takes it as it is).  Open3D's
+        sampler is unseeded; this one draws from the counter RNG of sample_points_uniformly, so `seed` fixes the
+        result."""
+        n = len(self._xyz)
+        if not (probability > 0.0 and probability <= 1.0):
+            raise RuntimeError("Probability must be > 0 and <= 1.0")
+        if ransac_n < 3:
+            raise RuntimeError("ransac_n should be set to higher than or equal to 3.")
+        if n < ransac_n:
+            raise RuntimeError("There must be at least 'ransac_n' points.")
+        if ransac_n > 32:
+            raise RuntimeError("[SegmentPlane] ransac_n > 32 is not supported by this build")
+        plane = np.zeros(4, np.float64)
+        idx = D.empty((n,), "int64")
+        k, evaluated = C.c_int64(0), C.c_int32(0)
+        L.call("ot_segment_plane", D.ptr(self._xyz.dev()), n, float(distance_threshold), int(ransac_n),
+               int(num_iterations), float(probability), int(seed) & 0xFFFFFFFFFFFFFFFF,
+               plane.ctypes.data_as(C.c_void_p), D.ptr(idx), C.byref(k), C.byref(evaluated), D.stream_ptr())
+        self._segment_plane_evaluated = evaluated.value  # iterations the loop counted (tests)
+        return plane, IntVector(D.to_host(idx[:k.value]).tolist())
+
     def compute_point_cloud_distance(self, target):
         """PointCloud::ComputePointCloudDistance (eval_cone.py:99,103) — ot_compute_point_cloud_distance.
         Per point of self: distance to the nearest point of `target` (float64); 0.0 when target is empty."""
