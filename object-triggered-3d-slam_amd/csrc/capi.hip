@@ -18,7 +18,7 @@ ot_status fail(ot_status code, const std::string& msg) {
     return code;
 }
 
-// Grow-only per-device scratch buffers, indexed by slot (a caller-chosen small integer).  Growth happens
+// Grow-only per-device scratch buffers, indexed by slot (scratch_slots.h).  Growth happens
 // with hipMalloc (synchronising) only when a larger request arrives; steady-state calls reuse the buffers.
 // Per host thread: threads driving their own streams (e.g. several objects reconstructed concurrently) never
 // share a buffer.  A thread's buffers live until the process ends (worker pools are long-lived).
@@ -32,7 +32,8 @@ static std::atomic<long long> g_allocs{0};
 void note_alloc() { g_allocs.fetch_add(1, std::memory_order_relaxed); }
 long long g_allocs_count() { return g_allocs.load(std::memory_order_relaxed); }
 
-void* scratch(size_t bytes, int slot) {
+void* scratch(size_t bytes, Slot slot_) {
+    const int slot = (int)slot_;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     if ((int)g_arena.size() <= dev) g_arena.resize(dev + 1);
@@ -62,7 +63,8 @@ void* scratch(size_t bytes, int slot) {
 
 static thread_local std::vector<Arena> g_pinned;
 
-void* pinned_scratch(size_t bytes, int slot, bool coherent) {
+void* pinned_scratch(size_t bytes, PinnedSlot slot_, bool coherent) {
+    const int slot = (int)slot_;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     if ((int)g_pinned.size() <= dev) g_pinned.resize(dev + 1);

@@ -94,25 +94,26 @@ struct KeyEmit {
     }
 };
 
+// unique_keys / unique_obj_keys: an error word, the keys and values of the sort (in / out)
+static auto keys_ws(size_t n) {
+    return carve(scratch_of(Slot::CHG_KEYS_WS), Arr<int>{1}, Arr<unsigned long long>{n}, Arr<unsigned long long>{n},
+                 Arr<unsigned>{n}, Arr<unsigned>{n});
+}
+
 // sorted unique lattice keys of a cloud -> uniq (device), count on the host
 static ot_status unique_keys(const double* xyz, int64_t n, double vs, const double o[3], unsigned long long* uniq,
-                             int64_t* nu, int slot, hipStream_t stream) {
+                             int64_t* nu, hipStream_t stream) {
     *nu = 0;
     if (n == 0) return OT_OK;
-    char* ws = (char*)scratch(256 + (size_t)n * (8 + 8 + 4 + 4), slot);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    int* err = (int*)ws;
-    unsigned long long* kin = (unsigned long long*)(ws + 256);
-    unsigned long long* kout = kin + n;
-    unsigned* vin = (unsigned*)(kout + n);
-    unsigned* vout = vin + n;
+    auto [err, kin, kout, vin, vout] = keys_ws((size_t)n);
+    if (!err) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemsetAsync(err, 0, sizeof(int), stream));
     hipLaunchKernelGGL(k_lattice_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, xyz, n, vs, o[0], o[1],
                        o[2], kin, vin, err);
     OT_LAUNCH_CHECK();
-    ot_status st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, 63, stream, 3);
+    ot_status st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, 63, stream, Slot::SORT_TMP);
     if (st != OT_OK) return st;
-    st = compact(n, UniqPred{kout}, UniqEmit{kout, uniq}, stream, nu, slot + 1);  // synchronises
+    st = compact(n, UniqPred{kout}, UniqEmit{kout, uniq}, stream, nu, Slot::CHG_KEYS_COMPACT);  // synchronises
     if (st != OT_OK) return st;
     int e = 0;
     OT_HIP_TRY(hipMemcpyAsync(&e, err, sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -200,17 +201,13 @@ struct ObjKeyEmit {
 
 // sorted unique object-lattice keys of the concatenated clouds of n_obj objects (offsets: host, n_obj + 1)
 static ot_status unique_obj_keys(const double* xyz, const int64_t* off, int n_obj, double vs, const double o[3],
-                                 const ObjLayout& lay, int end_bit, unsigned long long* uniq, int64_t* nu, int slot,
+                                 const ObjLayout& lay, int end_bit, unsigned long long* uniq, int64_t* nu,
                                  hipStream_t stream) {
     *nu = 0;
     const int64_t n = off[n_obj];
     if (n == 0) return OT_OK;
-    char* ws = (char*)scratch(256 + (size_t)n * (8 + 8 + 4 + 4), slot);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    unsigned long long* kin = (unsigned long long*)(ws + 256);
-    unsigned long long* kout = kin + n;
-    unsigned* vin = (unsigned*)(kout + n);
-    unsigned* vout = vin + n;
+    auto [err, kin, kout, vin, vout] = keys_ws((size_t)n);  // (no error word here: the bounds pass checked)
+    if (!err) return fail(OT_ERR_HIP, "scratch allocation failed");
     for (int j = 0; j < n_obj; ++j) {
         const int64_t m = off[j + 1] - off[j];
         if (m > 0)
@@ -218,9 +215,10 @@ static ot_status unique_obj_keys(const double* xyz, const int64_t* off, int n_ob
                                xyz + off[j] * 3, m, j, vs, o[0], o[1], o[2], lay, kin + off[j]);
     }
     OT_LAUNCH_CHECK();
-    ot_status st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, end_bit, stream, 3);  // values unused
+    ot_status st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, end_bit, stream,
+                                      Slot::SORT_TMP);  // values unused
     if (st != OT_OK) return st;
-    return compact(n, UniqPred{kout}, UniqEmit{kout, uniq}, stream, nu, slot + 1);  // synchronises
+    return compact(n, UniqPred{kout}, UniqEmit{kout, uniq}, stream, nu, Slot::CHG_KEYS_COMPACT);  // synchronises
 }
 
 // ------------------------------------------------------------------------------------------- scan diff
@@ -348,7 +346,7 @@ ot_status ot_grid_smart_paste(uint8_t* base, const uint8_t* overlay, int32_t hei
         return fail(OT_ERR_INVALID_ARGUMENT, "[smart_paste] invalid arguments");
     // 2d_selective_merge.py:59-60: a rectangle reaching outside the image leaves the base unchanged
     if (x < 0 || y < 0 || (int64_t)x + w > width || (int64_t)y + h > height || w <= 0 || h <= 0) return OT_OK;
-    unsigned long long* d = (unsigned long long*)scratch(64, 30);
+    unsigned long long* d = (unsigned long long*)scratch(64, Slot::CHG_PASTE_COUNT);
     if (!d) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemsetAsync(d, 0, sizeof(unsigned long long), stream));
     const int64_t nt = (int64_t)w * h;
@@ -374,22 +372,26 @@ ot_status ot_voxel_key_diff(const double* new_xyz, int64_t n, const double* old_
     if (!(voxel_size > 0.0)) return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] voxel_size <= 0.");
     if (n < 0 || m < 0 || (n > 0 && !new_xyz) || (m > 0 && !old_xyz) || n > 0x7FFFFFFF || m > 0x7FFFFFFF)
         return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] invalid buffers");
-    unsigned long long* ua = (unsigned long long*)scratch((size_t)std::max<int64_t>(n, 1) * 8 + 64, 31);
-    unsigned long long* ub = (unsigned long long*)scratch((size_t)std::max<int64_t>(m, 1) * 8 + 64, 32);
+    unsigned long long* ua =
+        (unsigned long long*)scratch((size_t)std::max<int64_t>(n, 1) * 8 + 64, Slot::CHG_UNIQ_NEW);
+    unsigned long long* ub =
+        (unsigned long long*)scratch((size_t)std::max<int64_t>(m, 1) * 8 + 64, Slot::CHG_UNIQ_OLD);
     if (!ua || !ub) return fail(OT_ERR_HIP, "scratch allocation failed");
     int64_t na = 0, nb = 0;
-    ot_status st = unique_keys(new_xyz, n, voxel_size, origin, ua, &na, 33, stream);
+    ot_status st = unique_keys(new_xyz, n, voxel_size, origin, ua, &na, stream);
     if (st != OT_OK) return st;
-    st = unique_keys(old_xyz, m, voxel_size, origin, ub, &nb, 33, stream);
+    st = unique_keys(old_xyz, m, voxel_size, origin, ub, &nb, stream);
     if (st != OT_OK) return st;
     if (na > 0) {
         if (!out_added) return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] out_added is NULL");
-        st = compact(na, AbsentPred{ua, ub, nb}, KeyEmit{ua, out_added}, stream, n_added_host, 35);
+        st = compact(na, AbsentPred{ua, ub, nb}, KeyEmit{ua, out_added}, stream, n_added_host,
+                     Slot::CHG_ADDED_COMPACT);
         if (st != OT_OK) return st;
     }
     if (nb > 0) {
         if (!out_removed) return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] out_removed is NULL");
-        st = compact(nb, AbsentPred{ub, ua, na}, KeyEmit{ub, out_removed}, stream, n_removed_host, 36);
+        st = compact(nb, AbsentPred{ub, ua, na}, KeyEmit{ub, out_removed}, stream, n_removed_host,
+                     Slot::CHG_REMOVED_COMPACT);
         if (st != OT_OK) return st;
     }
     return OT_OK;
@@ -409,12 +411,14 @@ ot_status ot_voxel_key_diff_multi(const double* new_xyz, const int64_t* new_offs
     const int64_t n = new_offsets[n_objects], m = old_offsets[n_objects];
     if (n < 0 || m < 0 || (n > 0 && !new_xyz) || (m > 0 && !old_xyz) || n > 0x7FFFFFFF || m > 0x7FFFFFFF)
         return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] invalid buffers");
-    unsigned long long* ua = (unsigned long long*)scratch((size_t)std::max<int64_t>(n, 1) * 8 + 64, 31);
-    unsigned long long* ub = (unsigned long long*)scratch((size_t)std::max<int64_t>(m, 1) * 8 + 64, 32);
+    unsigned long long* ua =
+        (unsigned long long*)scratch((size_t)std::max<int64_t>(n, 1) * 8 + 64, Slot::CHG_UNIQ_NEW);
+    unsigned long long* ub =
+        (unsigned long long*)scratch((size_t)std::max<int64_t>(m, 1) * 8 + 64, Slot::CHG_UNIQ_OLD);
     if (!ua || !ub) return fail(OT_ERR_HIP, "scratch allocation failed");
     if (n + m == 0) return OT_OK;
     // joint lattice bounds of both cloud sets -> the key layout
-    int* b6 = (int*)scratch(64, 37);
+    int* b6 = (int*)scratch(64, Slot::CHG_BOUNDS_POSES);
     if (!b6) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemsetAsync(b6, 0x7F, sizeof(int) * 3, stream));      // +large: minima
     OT_HIP_TRY(hipMemsetAsync(b6 + 3, 0x80, sizeof(int) * 3, stream));  // -large: maxima
@@ -430,11 +434,6 @@ ot_status ot_voxel_key_diff_multi(const double* new_xyz, const int64_t* new_offs
     OT_HIP_TRY(hipMemcpyAsync(hb, b6, sizeof(hb), hipMemcpyDeviceToHost, stream));
     OT_HIP_TRY(hipStreamSynchronize(stream));
     if (hb[6]) return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] lattice key out of range (voxel_size too small)");
-    auto bits_for = [](long long v) {  // bits to represent 0..v
-        int b = 1;
-        while (b < 62 && (v >> b) != 0) ++b;
-        return b;
-    };
     ObjLayout lay;
     int bx[3];
     for (int a = 0; a < 3; ++a) {
@@ -447,19 +446,20 @@ ot_status ot_voxel_key_diff_multi(const double* new_xyz, const int64_t* new_offs
     const int end_bit = lay.so + (n_objects > 1 ? bits_for(n_objects - 1) : 0);
     if (end_bit > 64) return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] lattice extent too large for 64-bit keys");
     int64_t na = 0, nb = 0;
-    ot_status st = unique_obj_keys(new_xyz, new_offsets, n_objects, voxel_size, origin, lay, end_bit, ua, &na, 33,
-                                   stream);
+    ot_status st = unique_obj_keys(new_xyz, new_offsets, n_objects, voxel_size, origin, lay, end_bit, ua, &na, stream);
     if (st != OT_OK) return st;
-    st = unique_obj_keys(old_xyz, old_offsets, n_objects, voxel_size, origin, lay, end_bit, ub, &nb, 33, stream);
+    st = unique_obj_keys(old_xyz, old_offsets, n_objects, voxel_size, origin, lay, end_bit, ub, &nb, stream);
     if (st != OT_OK) return st;
     if (na > 0) {
         if (!out_added) return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] out_added is NULL");
-        st = compact(na, AbsentPred{ua, ub, nb}, ObjKeyEmit{ua, out_added, lay}, stream, n_added_host, 35);
+        st = compact(na, AbsentPred{ua, ub, nb}, ObjKeyEmit{ua, out_added, lay}, stream, n_added_host,
+                     Slot::CHG_ADDED_COMPACT);
         if (st != OT_OK) return st;
     }
     if (nb > 0) {
         if (!out_removed) return fail(OT_ERR_INVALID_ARGUMENT, "[voxel_key_diff] out_removed is NULL");
-        st = compact(nb, AbsentPred{ub, ua, na}, ObjKeyEmit{ub, out_removed, lay}, stream, n_removed_host, 36);
+        st = compact(nb, AbsentPred{ub, ua, na}, ObjKeyEmit{ub, out_removed, lay}, stream, n_removed_host,
+                     Slot::CHG_REMOVED_COMPACT);
         if (st != OT_OK) return st;
     }
     return OT_OK;
@@ -493,8 +493,8 @@ ot_status ot_scan_diff(const float* real_ranges, const float* virtual_ranges, in
         cs[i] = make_float2(std::cos(ar), std::sin(ar));
         cs[(size_t)n_beams + i] = make_float2(std::cos(av), std::sin(av));
     }
-    ScanPose* dp = (ScanPose*)scratch(sizeof(ScanPose) * (size_t)n_scans + 64, 37);
-    float2* dcs = (float2*)scratch(sizeof(float2) * cs.size() + 64, 38);
+    ScanPose* dp = (ScanPose*)scratch(sizeof(ScanPose) * (size_t)n_scans + 64, Slot::CHG_BOUNDS_POSES);
+    float2* dcs = (float2*)scratch(sizeof(float2) * cs.size() + 64, Slot::CHG_SCAN_CS);
     if (!dp || !dcs) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemcpyAsync(dp, hp.data(), sizeof(ScanPose) * (size_t)n_scans, hipMemcpyHostToDevice, stream));
     OT_HIP_TRY(hipMemcpyAsync(dcs, cs.data(), sizeof(float2) * cs.size(), hipMemcpyHostToDevice, stream));
@@ -530,8 +530,8 @@ ot_status ot_virtual_scan(const int8_t* grid, int32_t height, int32_t width, flo
             cs[(size_t)b * n_beams + i] = make_double2(std::cos(g), std::sin(g));
         }
     }
-    double2* dcs = (double2*)scratch(sizeof(double2) * (size_t)nt + 64, 39);
-    double* drob = (double*)scratch(sizeof(double) * robot.size() + 64, 40);
+    double2* dcs = (double2*)scratch(sizeof(double2) * (size_t)nt + 64, Slot::CHG_GOAL_CS);
+    double* drob = (double*)scratch(sizeof(double) * robot.size() + 64, Slot::CHG_GOAL_ROBOT);
     if (!dcs || !drob) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemcpyAsync(dcs, cs.data(), sizeof(double2) * cs.size(), hipMemcpyHostToDevice, stream));
     OT_HIP_TRY(hipMemcpyAsync(drob, robot.data(), sizeof(double) * robot.size(), hipMemcpyHostToDevice, stream));

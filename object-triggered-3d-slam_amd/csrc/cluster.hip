@@ -172,17 +172,11 @@ ot_status ot_cluster_dbscan(const double* xyz, int64_t n, double eps, int32_t mi
     GridBuild gb;
     st = single_frame_grid(xyz, n, eps * ROR_CELL_SCALE, mn, mx, GRID_NBR3, stream, gb);
     if (st != OT_OK) return st;
-    // slot 12 (ROR's keep flags) and 13 (the compaction's block counts): neither the bounds nor the grid use them
-    const size_t n4 = ((size_t)n * 4 + 255) & ~(size_t)255, n1 = ((size_t)n + 255) & ~(size_t)255;
-    char* ws = (char*)scratch(5 * n4 + 2 * n1, 12);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    int* parent = (int*)ws;
-    int* comp = (int*)(ws + n4);
-    int* minidx = (int*)(ws + 2 * n4);
-    int* rank = (int*)(ws + 3 * n4);
-    int* clabel = (int*)(ws + 4 * n4);
-    unsigned char* core = (unsigned char*)(ws + 5 * n4);
-    unsigned char* flag = core + n1;
+    const size_t un = (size_t)n;
+    auto [parent, comp, minidx, rank, clabel, core, flag] =
+        carve(scratch_of(Slot::OP_WS), Arr<int>{un}, Arr<int>{un}, Arr<int>{un}, Arr<int>{un}, Arr<int>{un},
+              Arr<unsigned char>{un}, Arr<unsigned char>{un});
+    if (!parent) return fail(OT_ERR_HIP, "scratch allocation failed");
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     const double r2 = eps * eps;
     OT_HIP_TRY(hipMemsetAsync(flag, 0, (size_t)n, stream));
@@ -194,7 +188,7 @@ ot_status ot_cluster_dbscan(const double* xyz, int64_t n, double eps, int32_t mi
                        (const int*)minidx, flag);
     OT_LAUNCH_CHECK();
     int64_t nc = 0;
-    st = compact(n, FlagPred{flag}, RankEmit{rank}, stream, &nc, 13);
+    st = compact(n, FlagPred{flag}, RankEmit{rank}, stream, &nc, Slot::OP_COMPACT);
     if (st != OT_OK) return st;
     hipLaunchKernelGGL(k_db_corelabel, grid, block, 0, stream, n, (const unsigned char*)core, (const int*)comp,
                        (const int*)minidx, (const int*)rank, gb.g.sidx, clabel, out_labels);

@@ -8,6 +8,8 @@
 #include <string>
 
 #include "../../include/otslam.h"
+#include "scratch_slots.h"
+#include "workspace.h"
 
 namespace ot {
 
@@ -29,12 +31,16 @@ inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ----------------------------------------------------------------------------- per-device scratch
 // Grow-only scratch arena per host thread and device (capi.hip): threads driving their own streams never share a
-// buffer.
-void* scratch(size_t bytes, int slot);
+// buffer.  scratch_slots.h names the buffers and says who owns each.
+void* scratch(size_t bytes, Slot slot);
+// the buffer as carve()'s allocator (workspace.h)
+inline auto scratch_of(Slot slot) {
+    return [slot](size_t bytes) { return scratch(bytes, slot); };
+}
 // pinned host counterpart (per thread and device, grow-only): small tables uploaded with hipMemcpyAsync without the
 // pageable staging copy; the caller must have synchronised on its previous upload from the slot before rewriting it
 // coherent: fine-grained memory a kernel writes results into directly (a slot keeps the kind it was first made with)
-void* pinned_scratch(size_t bytes, int slot, bool coherent = false);
+void* pinned_scratch(size_t bytes, PinnedSlot slot, bool coherent = false);
 // a small host table (<= UPLOAD_ARG_BYTES) to device memory in stream order, carried by the kernel arguments of one
 // tiny launch instead of a copy command (measured: a ~1 KB hipMemcpyAsync from pinned memory took ~35 us on one
 // object's critical path beside a running kernel); larger tables take hipMemcpyAsync.  src is consumed on return.
@@ -86,6 +92,11 @@ __host__ __device__ inline void unpack_key(unsigned long long k, int& x, int& y,
     x = (int)((k >> 42) & 0x1FFFFF) - KEY_BIAS;
     y = (int)((k >> 21) & 0x1FFFFF) - KEY_BIAS;
     z = (int)(k & 0x1FFFFF) - KEY_BIAS;
+}
+__host__ __device__ inline int bits_for(long long v) {  // bits to represent 0..v
+    int b = 1;
+    while (b < 62 && (v >> b) != 0) ++b;
+    return b;
 }
 __host__ __device__ inline unsigned long long mix64(unsigned long long z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_emit(int64_t n, Pred pr
 
 // Host driver: runs the three launches on `stream` and returns the kept count on the host (synchronises).
 template <class Pred, class Emit>
-ot_status compact(int64_t n, Pred pred, Emit emit, hipStream_t stream, int64_t* n_out_host, int scratch_slot) {
+ot_status compact(int64_t n, Pred pred, Emit emit, hipStream_t stream, int64_t* n_out_host, Slot scratch_slot) {
     const int64_t nblocks = (n + CMP_TILE - 1) / CMP_TILE;
     if (n <= 0) {
         *n_out_host = 0;
@@ -213,7 +213,7 @@ struct SegHeadEmit {
 
 // Host driver of k_segments_emit (count with SegHeadPred, scan, emit); returns the segment count (synchronises).
 inline ot_status compact_segments(int64_t n, const unsigned long long* keys, int* heads, int* seg, hipStream_t stream,
-                                  int64_t* n_seg_host, int scratch_slot) {
+                                  int64_t* n_seg_host, Slot scratch_slot) {
     const int64_t nblocks = (n + CMP_TILE - 1) / CMP_TILE;
     *n_seg_host = 0;
     if (n <= 0) return OT_OK;

@@ -20,7 +20,7 @@
 //   k_fb_reduce   one lane per voxel: its points re-unprojected from their records (no xyz/rgb intermediates in HBM,
 //                 one 8-B gather per point), summed in index order, divided by the count (Open3D AccumulatedPoint);
 //                 also the voxel's SOR cell key
-//   SOR           grid.h over all frames' voxel clouds at once (frame in the key's top bits) + sor_frames.  The SOR
+//   SOR           grid.h over all frames' voxel clouds at once (frame in the key's top bits) + sor.h's sor_frames.  The SOR
 //                 cells are blocks of 2^m x 2^m x 2^m voxels on the voxel lattice (m from nb_neighbors: ~0.9 k points
 //                 per occupied cell of a surface), so the voxel order IS the grid's cell order: the grid is built
 //                 from the voxel list directly (cell heads, column hash, neighbour ranges) -- no cell keys from the
@@ -33,7 +33,7 @@
 #include <vector>
 
 #include "compact.h"
-#include "grid.h"
+#include "sor.h"
 #include "sort.h"
 
 namespace ot {
@@ -949,13 +949,13 @@ ot_status ot_rgbd_filter_run(ot_rgbd_filter* fl, int32_t n_frames, const uint16_
         hipLaunchKernelGGL(k_fb_runs, dim3(tpf, F), dim3(FB_THREADS), 0, stream, p, kb, (const int*)d_tc,
                            (const int*)d_poff, k32, vin, packed, d_status, d_ticket, d_rlen);
         OT_LAUNCH_CHECK();
-        st = sort_segments_u32_u32(k32, k32o, vin, vout, fl->poff.data(), F, vbits, stream, 3, d_rlen);
+        st = sort_segments_u32_u32(k32, k32o, vin, vout, fl->poff.data(), F, vbits, stream, Slot::SORT_TMP, d_rlen);
         if (st != OT_OK) return st;
         // voxel heads frame by frame: count per (chunk, frame), one scan, emit; sync 2 reads the total
         int maxpts = 0;
         for (int f = 0; f < F; ++f) maxpts = std::max(maxpts, (int)(fl->poff[f + 1] - fl->poff[f]));
         const int chunks = std::max(1, (maxpts + FB_HEAD_CHUNK - 1) / FB_HEAD_CHUNK);
-        char* ws = (char*)scratch(sizeof(int) * (size_t)chunks * F + 64, 7);
+        char* ws = (char*)scratch(sizeof(int) * (size_t)chunks * F + 64, Slot::VOXEL_HEADS);
         if (!ws) return fail(OT_ERR_HIP, "[rgbd_filter] allocation failed");
         int64_t* d_total = (int64_t*)ws;
         int* d_hc = (int*)(ws + 64);
@@ -986,18 +986,18 @@ ot_status ot_rgbd_filter_run(ot_rgbd_filter* fl, int32_t n_frames, const uint16_
         hipLaunchKernelGGL((k_fb_keys<unsigned>), dim3(tpf, F), dim3(FB_THREADS), 0, stream, p, kt, (const int*)d_tc,
                            k32, vin);
         OT_LAUNCH_CHECK();
-        st = sort_segments_u32_u32(k32, k32o, vin, vout, fl->poff.data(), F, vbits, stream, 3);
+        st = sort_segments_u32_u32(k32, k32o, vin, vout, fl->poff.data(), F, vbits, stream, Slot::SORT_TMP);
         if (st != OT_OK) return st;
-        if (kt.tag) st = compact(P, SegHeadPredTag{k32o}, SegHeadEmit{heads}, stream, &K, 7);  // sync 2
-        else st = compact(P, SegHeadPredPix{k32o, vout, (unsigned)npx}, SegHeadEmit{heads}, stream, &K, 7);
+        if (kt.tag) st = compact(P, SegHeadPredTag{k32o}, SegHeadEmit{heads}, stream, &K, Slot::VOXEL_HEADS);  // sync 2
+        else st = compact(P, SegHeadPredPix{k32o, vout, (unsigned)npx}, SegHeadEmit{heads}, stream, &K, Slot::VOXEL_HEADS);
         if (st != OT_OK) return st;
     } else {
         hipLaunchKernelGGL((k_fb_keys<unsigned long long>), dim3(tpf, F), dim3(FB_THREADS), 0, stream, p, kb,
                            (const int*)d_tc, kin, vin);
         OT_LAUNCH_CHECK();
-        st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)P, end_bit, stream, 3);
+        st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)P, end_bit, stream, Slot::SORT_TMP);
         if (st != OT_OK) return st;
-        st = compact(P, SegHeadPred{kout}, SegHeadEmit{heads}, stream, &K, 7);  // synchronises (sync 2)
+        st = compact(P, SegHeadPred{kout}, SegHeadEmit{heads}, stream, &K, Slot::VOXEL_HEADS);  // synchronises (sync 2)
         if (st != OT_OK) return st;
     }
     if (!pack)
@@ -1037,20 +1037,20 @@ ot_status ot_rgbd_filter_run(ot_rgbd_filter* fl, int32_t n_frames, const uint16_
     GridBuild gb;
     OT_HIP_TRY(hipStreamSynchronize(stream));  // hvoff (copied above) is needed on the host from here
     st = build_grid_sorted(fl->vx, ckeys, K, F, d_voff, d_org, hcell, cbits, SOR_GRID_NBR, stream, gb,
-                           25);  // synchronises
+                           BATCH_GRID_SLOTS);  // synchronises
     if (st != OT_OK) return st;
     for (int f = 0; f <= F; ++f) fl->voff[f] = hvoff[f];
     double* avg = (double*)fl->b_avg.get((size_t)K * 8 + (size_t)F * 32 + 256);
     if (!avg) return fail(OT_ERR_HIP, "[rgbd_filter] allocation failed");
     fl->avg = avg;
     double* stats = avg + K;
-    st = sor_frames(gb, K, hvoff.data(), fl->nb_neighbors, fl->std_ratio, avg, stats, stream, 28);
+    st = sor_frames(gb, K, hvoff.data(), fl->nb_neighbors, fl->std_ratio, avg, stats, stream, BATCH_SOR_SLOTS);
     if (st != OT_OK) return st;
     // ---- kept voxels: indices, per-frame offsets, rows ------------------------------------------------------
     int64_t* kept = (int64_t*)fl->b_out.get((size_t)K * (8 + 8 + 48) + (size_t)(F + 1) * 8 + 512);
     if (!kept) return fail(OT_ERR_HIP, "[rgbd_filter] allocation failed");
     int64_t nk = 0;
-    st = compact(K, SorKeep{avg, stats, d_voff, F}, KeptEmit{kept}, stream, &nk, 13);  // synchronises
+    st = compact(K, SorKeep{avg, stats, d_voff, F}, KeptEmit{kept}, stream, &nk, Slot::OP_COMPACT);  // synchronises
     if (st != OT_OK) return st;
     fl->kept = nk;
     int64_t* d_koff = kept + K;

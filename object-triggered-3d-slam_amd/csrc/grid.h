@@ -1,4 +1,5 @@
-// grid.h — multi-frame neighbour grid shared by outlier.hip (single clouds) and filter_batch.hip (frame batches).
+// grid.h — the multi-frame neighbour grid (built by grid.hip) under SOR, ROR, cloud distance, DBSCAN, normals, ICP and
+// the batch filter.
 //
 // A cloud of n points grouped in F frames (frame f = point indices [foff[f], foff[f+1])) is binned into cubic cells
 // of size h anchored at a per-frame origin.  Keys pack (frame, x, y, z) with z in the low bits, so a frame's points
@@ -16,15 +17,6 @@ namespace ot {
 constexpr int NBR3 = 9;   // 3x3 columns, z-1 .. z+1
 constexpr int NBR5 = 25;  // 5x5 columns, z-2 .. z+2
 
-// SOR (outlier.hip): radius (in cells) of the block a query scans first, and the matching cell occupancy target
-// (points per occupied cell of a surface-like cloud); both only change speed, never a result.  Measured and settled
-// (DESIGN.md §4): R = 2 with finer cells, occupancies 0.6-1.3 k, precomputed 5x5 ranges for stage 2 -- all slower.
-constexpr int SOR_BLOCK_R = 1;
-inline double sor_cell_target(int nb_neighbors) {
-    const double t = 0.9 * (double)nb_neighbors;
-    return t > 2.0 ? t : 2.0;
-}
-
 // ROR (outlier.hip): cells are this factor wider than the radius.  A point's cell is floor((v - origin) / h) with the
 // subtraction and the division each rounded, so the computed cell quotients of two points d apart differ from d / h by
 // up to 2^-31 (each quotient is below 2^20 cells and carries two roundings of 2^-53 relative).  With h = radius
@@ -35,7 +27,6 @@ constexpr double ROR_CELL_SCALE = 1.0 + 1.0 / (double)(1 << 20);
 
 // neighbour structures a grid build can precompute (bit mask)
 enum { GRID_NBR3 = 1, GRID_NBR5 = 2 };
-constexpr int SOR_GRID_NBR = GRID_NBR3;
 
 struct GridDev {
     const double* sxyz;        // [n][3] points in sorted (frame, cell) order
@@ -62,7 +53,7 @@ struct GridBuild {
     int64_t ncells = 0;
 };
 
-// ---- device lookups (shared by outlier.hip and icp.hip) ----------------------------------------------------------
+// ---- device lookups ----------------------------------------------------------------------------------------------
 __device__ inline int cell_coord(double v, double origin, double h) { return (int)floor((v - origin) / h); }
 
 __device__ inline bool cell_valid(const GridDev& g, int x, int y, int z) {
@@ -152,61 +143,37 @@ __device__ inline double block_guard(const GridDev& g, const double q[3], const 
 // Build the grid of n points (xyz device [n][3]) grouped in nframes frames.  d_foff / d_origin: device arrays
 // ([F+1] ints, [F][3] doubles) that must outlive the grid; dims: cells per axis covering every frame; nbr: the
 // GRID_* structures to precompute; h_foff (optional host copy of the frame offsets, <= 64 frames): the cell sort
-// runs per frame (segmented, cell bits only) instead of over frame-prefixed keys.  Scratch
-// slots slot0 .. slot0 + 2.  Synchronises (cell count).
+// runs per frame (segmented, cell bits only) instead of over frame-prefixed keys.  Synchronises (cell count).
 ot_status build_grid_frames(const double* xyz, int64_t n, int nframes, const int* d_foff, const double* d_origin,
-                            double h, const int dims[3], int nbr, hipStream_t stream, GridBuild& out, int slot0,
-                            const int* h_foff = nullptr);
+                            double h, const int dims[3], int nbr, hipStream_t stream, GridBuild& out,
+                            const GridSlots& slots, const int* h_foff = nullptr);
 
 // The grid of a cloud already in cell order (filter_batch.hip: voxels sorted by cell-major keys): ckeys[i] = point i's
 // cell key (frame << (bits[0] + bits[1] + bits[2]) | x << (bits[1] + bits[2]) | y << bits[2] | z, non-decreasing),
-// cells of edge h at the per-frame origins; no sort, no copy (the grid reads xyz in place).  Scratch slots slot0 ..
-// slot0 + 2.  Synchronises (cell count).
+// cells of edge h at the per-frame origins; no sort, no copy (the grid reads xyz in place).  Synchronises (cell
+// count).
 ot_status build_grid_sorted(const double* xyz, const unsigned long long* ckeys, int64_t n, int nframes,
                             const int* d_foff, const double* d_origin, double h, const int bits[3], int nbr,
-                            hipStream_t stream, GridBuild& out, int slot0);
+                            hipStream_t stream, GridBuild& out, const GridSlots& slots);
 
-// Statistical outlier removal over a built grid (Open3D RemoveStatisticalOutliers per frame):
-// avg[i] = mean kNN distance of point i (-1 when none); per frame the cloud mean and squared-deviation sum are
-// Open3D's sequential float64 accumulations (exact chains), stats[f] = {mean, std, valid, threshold}.
-// h_foff: host copy of the frame offsets.  Scratch slots slot0 .. slot0 + 1.  Synchronises once (job table).
-ot_status sor_frames(const GridBuild& gb, int64_t n, const int* h_foff, int nb_neighbors, double std_ratio,
-                     double* avg, double* stats, hipStream_t stream, int slot0);
-
-// The statistics half of sor_frames: from the mean kNN distances avg[0 .. n) (frame-major, d_foff / h_foff: device /
-// host frame offsets) to stats[f] = {mean, std, valid, threshold}.  Scratch slot `slot`.  Synchronises once.
-ot_status sor_stats_frames(const double* avg, const int* d_foff, const int* h_foff, int F, double std_ratio,
-                           double* stats, hipStream_t stream, int slot);
-
-// per-axis bounds of a device cloud on the host (scratch slots 11, 19).  Synchronises.
+// per-axis bounds of a device cloud on the host.  Synchronises.
 ot_status bounds_host(const double* xyz, int64_t n, hipStream_t stream, double mn[3], double mx[3]);
 
-// one frame: origin = the cloud's minimum corner, cells per axis from the extent (scratch slots 20, 22 .. 24)
+// one frame: origin = the cloud's minimum corner, cells per axis from the extent (the cloud grid's buffers)
 ot_status single_frame_grid(const double* xyz, int64_t n, double h, const double mn[3], const double mx[3], int nbr,
                             hipStream_t stream, GridBuild& gb);
 
-// The grid a cross-cloud nearest-neighbour search runs over (ComputePointCloudDistance, registration): the target's
-// bounds and cells sized for ~4 target points per occupied cell of a surface-like cloud, refined once from the
-// measured occupancy.  The grid only changes speed, never a result.  Scratch slots as above.  Synchronises.
-ot_status nn_target_grid(const double* tgt, int64_t m, int nbr, hipStream_t stream, double mn[3], double mx[3],
-                         GridBuild& gb);
+// The single-frame grid of a cloud (n > 0) with cells sized for ~target points per occupied cell of a surface-like
+// cloud, rebuilt once from the measured occupancy when that is off by more than 2.5x; mn / mx receive the cloud's
+// bounds.  The grid only changes speed, never a result.  Synchronises.
+ot_status occupancy_grid(const double* xyz, int64_t n, double target, int nbr, double mn[3], double mx[3],
+                         hipStream_t stream, GridBuild& gb);
 
-// keep predicate of frame f's points: avg > 0 && avg < stats[f].threshold
-struct SorKeep {
-    const double* avg;
-    const double* stats;  // [F][4]
-    const int* foff;
-    int nframes;
-    __device__ inline bool operator()(int64_t i) const {
-        int lo = 0, hi = nframes;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (foff[mid] <= i) lo = mid;
-            else hi = mid;
-        }
-        const double a = avg[i];
-        return a > 0 && a < stats[lo * 4 + 3];
-    }
-};
+// The grid a cross-cloud nearest-neighbour search runs over (ComputePointCloudDistance, registration): ~4 target
+// points per occupied cell.
+inline ot_status nn_target_grid(const double* tgt, int64_t m, int nbr, hipStream_t stream, double mn[3], double mx[3],
+                                GridBuild& gb) {
+    return occupancy_grid(tgt, m, 4.0, nbr, mn, mx, stream, gb);
+}
 
 }  // namespace ot

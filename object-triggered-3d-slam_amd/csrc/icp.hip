@@ -32,8 +32,6 @@ namespace ot {
 constexpr int ICP_CHUNK = 8;
 constexpr int ICP_NSUM = 17;  // k, sum d2, sp[3], sq[3], spq[9]
 constexpr int ICP_TILE = 128;  // partial records the solve stages in LDS at a time
-// scratch slots (the grid build holds 11, 19, 20, 22-24; the compaction 13)
-constexpr int ICP_SLOT_PCD = 50, ICP_SLOT_NN = 51, ICP_SLOT_PART = 52, ICP_SLOT_MAIL = 53;
 
 struct IcpState {
     double T[16];       // accumulated transformation (row-major)
@@ -424,15 +422,15 @@ static ot_status icp_run(const double* src, int64_t n, const double* tgt, int64_
                                     (double)std::max(gb.g.dim[0], std::max(gb.g.dim[1], gb.g.dim[2])));
 
     const int nblocks = (int)((n + 255) / 256);
-    double* pcd = (double*)scratch((size_t)n * 24 + 64, ICP_SLOT_PCD);
-    char* nn = (char*)scratch((size_t)n * 12 + 256, ICP_SLOT_NN);
-    char* pw = (char*)scratch((size_t)nblocks * ICP_NSUM * 8 + sizeof(IcpState) + 256, ICP_SLOT_PART);
-    unsigned* mail = (unsigned*)pinned_scratch(2 * 4 * (ICP_MAIL_WORDS + 2), ICP_SLOT_MAIL, true);
-    if (!pcd || !nn || !pw || !mail) return fail(OT_ERR_HIP, "scratch allocation failed");
-    double* d2 = (double*)nn;
-    int* idx = (int*)(d2 + n);
-    IcpState* dst = (IcpState*)pw;
-    double* part = (double*)(pw + ((sizeof(IcpState) + 63) & ~(size_t)63));
+    double* pcd = (double*)scratch((size_t)n * 24 + 64, Slot::ICP_PCD);
+    double *d2, *part;  // (plain pointers: the iteration lambda below captures them)
+    int* idx;
+    IcpState* dst;
+    std::tie(d2, idx) = carve(scratch_of(Slot::ICP_NN), Arr<double>{(size_t)n}, Arr<int>{(size_t)n});
+    std::tie(dst, part) =
+        carve(scratch_of(Slot::ICP_PARTIALS), Arr<IcpState>{1}, Arr<double>{(size_t)nblocks * ICP_NSUM});
+    unsigned* mail = (unsigned*)pinned_scratch(2 * 4 * (ICP_MAIL_WORDS + 2), PinnedSlot::ICP_MAIL, true);
+    if (!pcd || !d2 || !dst || !mail) return fail(OT_ERR_HIP, "scratch allocation failed");
     unsigned* mbox[2] = {mail, mail + ICP_MAIL_WORDS + 2};
     mbox[0][ICP_MAIL_WORDS] = 0;  // sequence words start below every seq sent (nothing of an earlier call is in flight)
     mbox[1][ICP_MAIL_WORDS] = 0;
@@ -500,7 +498,7 @@ static ot_status icp_run(const double* src, int64_t n, const double* tgt, int64_
     if (n_corr) *n_corr = hs.k;
     if (corr) {
         int64_t k = 0;
-        st = compact(n, CorrPred{idx}, CorrEmit{idx, corr}, stream, &k, 13);  // synchronises
+        st = compact(n, CorrPred{idx}, CorrEmit{idx, corr}, stream, &k, Slot::OP_COMPACT);  // synchronises
         if (st != OT_OK) return st;
         if (n_corr) *n_corr = k;
     } else {

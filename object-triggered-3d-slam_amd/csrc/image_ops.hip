@@ -198,7 +198,7 @@ ot_status ot_unproject(const float* depth, const uint8_t* color, const ot_intrin
     inverse4(extrinsic, emit.pose.m);
     emit.xyz = out_xyz;
     emit.rgb = out_rgb;
-    return compact(n, pred, emit, S(stream), n_points_host, 0);
+    return compact(n, pred, emit, S(stream), n_points_host, Slot::IMG_UNPROJECT_COMPACT);
 }
 
 ot_status ot_filter_min_z(const double* xyz, const double* rgb, int64_t n, double z_min, double* out_xyz,
@@ -207,7 +207,7 @@ ot_status ot_filter_min_z(const double* xyz, const double* rgb, int64_t n, doubl
         return fail(OT_ERR_INVALID_ARGUMENT, "[filter_min_z] invalid arguments");
     MinZPred pred{xyz, z_min};
     CopyRowsEmit emit{xyz, rgb, out_xyz, out_rgb};
-    return compact(n, pred, emit, S(stream), n_out_host, 1);
+    return compact(n, pred, emit, S(stream), n_out_host, Slot::IMG_MIN_Z_COMPACT);
 }
 
 ot_status ot_gather_rows3(const double* in, const int64_t* idx, int64_t m, double* out, void* stream) {
@@ -225,7 +225,7 @@ ot_status ot_occupancy_to_points(const uint8_t* img, int32_t height, int32_t wid
         return fail(OT_ERR_INVALID_ARGUMENT, "[create_map_cloud] invalid arguments");
     OccPred pred{img, threshold};
     OccEmit emit{width, height, resolution, origin_x, origin_y, out_xyz};
-    return compact((int64_t)width * height, pred, emit, S(stream), n_out_host, 2);
+    return compact((int64_t)width * height, pred, emit, S(stream), n_out_host, Slot::IMG_OCCUPANCY_COMPACT);
 }
 
 }  // extern "C"

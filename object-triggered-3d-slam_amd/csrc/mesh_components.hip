@@ -34,9 +34,6 @@
 
 namespace ot {
 
-// scratch slots no other call of the library uses (nothing here runs beside another of these on one host thread)
-constexpr int MCC_SLOT_WS = 70, MCC_SLOT_COMPACT = 71, MCC_SLOT_BAD = 72;
-constexpr int MCC_SLOT_SORT = 3;  // the sort's temporaries, as every sort of the library
 
 static int index_bits(int64_t nv) {  // bit width of the largest valid index, nv <= 2^31 - 1
     int b = 1;
@@ -256,7 +253,7 @@ static ot_status check_sizes(const char* who, int64_t nt, int64_t nv) {
 // the range check over the triangle array alone (synchronises)
 static ot_status check_indices(const char* who, const int32_t* T, int64_t nt, int64_t nv, hipStream_t stream) {
     if (nt == 0) return OT_OK;
-    int* bad = (int*)scratch(64, MCC_SLOT_BAD);
+    int* bad = (int*)scratch(64, Slot::MCC_BAD);
     if (!bad) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), stream));
     hipLaunchKernelGGL(k_mcc_range, blocks_of(nt * 3), dim3(256), 0, stream, T, nt * 3, nv, bad);
@@ -267,8 +264,6 @@ static ot_status check_indices(const char* who, const int32_t* T, int64_t nt, in
     if (h) return fail(OT_ERR_INVALID_ARGUMENT, std::string("[") + who + "] triangle index out of range [0, n_vertices)");
     return OT_OK;
 }
-
-static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace ot
 
@@ -293,39 +288,31 @@ ot_status ot_mesh_cluster_connected_triangles(const int32_t* triangles, int64_t 
     st = check_indices(who, triangles, nt, nv, stream);
     if (st != OT_OK) return st;
     const int64_t m = nt * 3;
-    const size_t n4 = up256((size_t)nt * 4 + 4), n1 = up256((size_t)nt), n8 = up256((size_t)nt * 8);
-    const size_t m8 = up256((size_t)m * 8), m4 = up256((size_t)m * 4);
-    char* ws = (char*)scratch(4 * n4 + n1 + 2 * n8 + 2 * m8 + 2 * m4, MCC_SLOT_WS);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    int* parent = (int*)ws;
-    int* comp = (int*)(ws + n4);
-    int* rank = (int*)(ws + 2 * n4);
-    int* start = (int*)(ws + 3 * n4);  // nt + 1 entries
-    unsigned char* flag = (unsigned char*)(ws + 4 * n4);
-    double* area = (double*)(ws + 4 * n4 + n1);
-    double* sarea = vertices ? (double*)(ws + 4 * n4 + n1 + n8) : nullptr;
-    unsigned long long* kin = (unsigned long long*)(ws + 4 * n4 + n1 + 2 * n8);
-    unsigned long long* kout = (unsigned long long*)((char*)kin + m8);
-    unsigned* vin = (unsigned*)((char*)kout + m8);
-    unsigned* vout = (unsigned*)((char*)vin + m4);
+    const size_t unt = (size_t)nt, um = (size_t)m;
+    auto [parent, comp, rank, start, flag, area, sarea_ws, kin, kout, vin, vout] =
+        carve(scratch_of(Slot::MCC_WS), Arr<int>{unt}, Arr<int>{unt}, Arr<int>{unt}, Arr<int>{unt + 1},
+              Arr<unsigned char>{unt}, Arr<double>{unt}, Arr<double>{unt}, Arr<unsigned long long>{um},
+              Arr<unsigned long long>{um}, Arr<unsigned>{um}, Arr<unsigned>{um});
+    if (!parent) return fail(OT_ERR_HIP, "scratch allocation failed");
+    double* sarea = vertices ? sarea_ws : nullptr;
     const int bits = index_bits(nv);
     hipLaunchKernelGGL(k_mcc_edges, blocks_of(nt), dim3(256), 0, stream, triangles, nt, bits, kin, vin, parent);
     OT_LAUNCH_CHECK();
-    st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)m, 2 * bits, stream, MCC_SLOT_SORT);
+    st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)m, 2 * bits, stream, Slot::SORT_TMP);
     if (st != OT_OK) return st;
     hipLaunchKernelGGL(k_mcc_hook, blocks_of(m), dim3(256), 0, stream, (const unsigned long long*)kout,
                        (const unsigned*)vout, m, parent);
     hipLaunchKernelGGL(k_mcc_flatten, blocks_of(nt), dim3(256), 0, stream, nt, parent, comp, flag);
     OT_LAUNCH_CHECK();
     int64_t nc = 0;
-    st = compact(nt, ByteSetPred{flag}, RankOfEmit{rank}, stream, &nc, MCC_SLOT_COMPACT);
+    st = compact(nt, ByteSetPred{flag}, RankOfEmit{rank}, stream, &nc, Slot::MCC_COMPACT);
     if (st != OT_OK) return st;
     hipLaunchKernelGGL(k_mcc_label, blocks_of(nt), dim3(256), 0, stream, nt, (const int*)comp, (const int*)rank,
                        vertices, triangles, out_triangle_clusters, kin, vin, area);
     OT_LAUNCH_CHECK();
     int lbits = 1;
     while (lbits < 31 && ((nc - 1) >> lbits) != 0) ++lbits;
-    st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)nt, lbits, stream, MCC_SLOT_SORT);
+    st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)nt, lbits, stream, Slot::SORT_TMP);
     if (st != OT_OK) return st;
     hipLaunchKernelGGL(k_mcc_starts, blocks_of(nt), dim3(256), 0, stream, (const unsigned long long*)kout,
                        (const unsigned*)vout, nt, nc, start, (const double*)area, sarea);
@@ -367,22 +354,19 @@ ot_status ot_mesh_flag_duplicated_triangles(const int32_t* triangles, int64_t n_
     if (nt == 0) return OT_OK;
     st = check_indices(who, triangles, nt, n_vertices, stream);
     if (st != OT_OK) return st;
-    const size_t t8 = up256((size_t)nt * 8), t4 = up256((size_t)nt * 4);
-    char* ws = (char*)scratch(2 * t8 + 2 * t4, MCC_SLOT_WS);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    unsigned long long* ka = (unsigned long long*)ws;
-    unsigned long long* kb = (unsigned long long*)(ws + t8);
-    unsigned* va = (unsigned*)(ws + 2 * t8);
-    unsigned* vb = (unsigned*)(ws + 2 * t8 + t4);
+    const size_t unt = (size_t)nt;
+    auto [ka, kb, va, vb] = carve(scratch_of(Slot::MCC_WS), Arr<unsigned long long>{unt}, Arr<unsigned long long>{unt},
+                                  Arr<unsigned>{unt}, Arr<unsigned>{unt});
+    if (!ka) return fail(OT_ERR_HIP, "scratch allocation failed");
     const int bits = index_bits(n_vertices);
     hipLaunchKernelGGL(k_mcc_dup_k2, blocks_of(nt), dim3(256), 0, stream, triangles, nt, ka, va);
     OT_LAUNCH_CHECK();
-    st = sort_pairs_u64_u32(ka, kb, va, vb, (size_t)nt, bits, stream, MCC_SLOT_SORT);  // by the third component
+    st = sort_pairs_u64_u32(ka, kb, va, vb, (size_t)nt, bits, stream, Slot::SORT_TMP);  // by the third component
     if (st != OT_OK) return st;
     hipLaunchKernelGGL(k_mcc_dup_k01, blocks_of(nt), dim3(256), 0, stream, triangles, nt, bits, (const unsigned*)vb,
                        ka);
     OT_LAUNCH_CHECK();
-    st = sort_pairs_u64_u32(ka, kb, vb, va, (size_t)nt, 2 * bits, stream, MCC_SLOT_SORT);  // then by the first two
+    st = sort_pairs_u64_u32(ka, kb, vb, va, (size_t)nt, 2 * bits, stream, Slot::SORT_TMP);  // then by the first two
     if (st != OT_OK) return st;
     hipLaunchKernelGGL(k_mcc_dup_flag, blocks_of(nt), dim3(256), 0, stream, triangles, nt, (const unsigned*)va,
                        out_remove_mask);
@@ -402,7 +386,7 @@ ot_status ot_mesh_remove_triangles_by_mask(const int32_t* triangles, int64_t n_t
     *n_kept_host = 0;
     if (n_triangles == 0) return OT_OK;
     return compact(n_triangles, ByteClearPred{remove_mask}, TriEmit{triangles, out_triangles}, stream, n_kept_host,
-                   MCC_SLOT_COMPACT);
+                   Slot::MCC_COMPACT);
 }
 
 ot_status ot_mesh_remove_unreferenced_vertices(int64_t n_vertices, int32_t* triangles, int64_t n_triangles,
@@ -418,17 +402,14 @@ ot_status ot_mesh_remove_unreferenced_vertices(int64_t n_vertices, int32_t* tria
     st = check_indices(who, triangles, nt, nv, stream);  // (no vertices and a triangle: refused here)
     if (st != OT_OK) return st;
     if (nv == 0 || nt == 0) return OT_OK;  // no triangle references anything
-    const size_t v1 = up256((size_t)nv);
-    char* ws = (char*)scratch(v1 + up256((size_t)nv * 4), MCC_SLOT_WS);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    unsigned char* flag = (unsigned char*)ws;
-    int* newidx = (int*)(ws + v1);
+    auto [flag, newidx] = carve(scratch_of(Slot::MCC_WS), Arr<unsigned char>{(size_t)nv}, Arr<int>{(size_t)nv});
+    if (!flag) return fail(OT_ERR_HIP, "scratch allocation failed");
     const int64_t m = nt * 3;
     OT_HIP_TRY(hipMemsetAsync(flag, 0, (size_t)nv, stream));
     hipLaunchKernelGGL(k_mcc_mark, blocks_of(m), dim3(256), 0, stream, (const int32_t*)triangles, m, flag);
     OT_LAUNCH_CHECK();
     st = compact(nv, ByteSetPred{flag}, KeptVertexEmit{out_kept_old_index, newidx}, stream, n_kept_host,
-                 MCC_SLOT_COMPACT);
+                 Slot::MCC_COMPACT);
     if (st != OT_OK) return st;
     hipLaunchKernelGGL(k_mcc_renumber, blocks_of(m), dim3(256), 0, stream, triangles, m, (const int*)newidx);
     OT_LAUNCH_CHECK();

@@ -977,14 +977,11 @@ ot_status ot_mesh_compute_vertex_normals(const double* V, int64_t nv, const int3
     if (nv == 0) return OT_OK;
     const int64_t m = nt * 3;
     if (m > 0x7FFFFFFF || nv > 0x7FFFFFFF) return fail(OT_ERR_INVALID_ARGUMENT, "[ComputeVertexNormals] mesh too large");
-    char* ws = (char*)scratch((size_t)nt * 24 + (size_t)m * (8 + 8 + 4 + 4) + (size_t)nv * 4 + 1024, 16);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    double* TN = (double*)ws;
-    unsigned long long* kin = (unsigned long long*)(TN + nt * 3);
-    unsigned long long* kout = kin + m;
-    unsigned* vin = (unsigned*)(kout + m);
-    unsigned* vout = vin + m;
-    int* start = (int*)(vout + m);
+    const size_t um = (size_t)m;
+    auto [TN, kin, kout, vin, vout, start] =
+        carve(scratch_of(Slot::MESH_NORMALS_WS), Arr<double>{um}, Arr<unsigned long long>{um},
+              Arr<unsigned long long>{um}, Arr<unsigned>{um}, Arr<unsigned>{um}, Arr<int>{(size_t)nv});
+    if (!TN) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemsetAsync(start, 0xFF, sizeof(int) * nv, stream));
     if (nt > 0) {
         hipLaunchKernelGGL(k_tri_normals, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, stream, V, T, nt, TN, kin,
@@ -992,7 +989,7 @@ ot_status ot_mesh_compute_vertex_normals(const double* V, int64_t nv, const int3
         OT_LAUNCH_CHECK();
         int bits = 1;
         while (bits < 63 && (nv >> bits) != 0) ++bits;
-        ot_status st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)m, bits, stream, 3);
+        ot_status st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)m, bits, stream, Slot::SORT_TMP);
         if (st != OT_OK) return st;
         hipLaunchKernelGGL(k_vertex_starts, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, kout, m, start);
     }
@@ -1029,8 +1026,8 @@ struct HiStream {
     int dev = -1;
 };
 static thread_local HiStream g_hi;
-// ot_mesh_sample_points_min_z_async's pending call on this thread: its tables live in this thread's scratch slot 17 and
-// pinned slots 0 / 1 until ot_mesh_sample_points_min_z_wait, so no other sampling may start on the thread before
+// ot_mesh_sample_points_min_z_async's pending call on this thread: its tables live in this thread's sampler workspace
+// and pinned buffers until ot_mesh_sample_points_min_z_wait, so no other sampling may start on the thread before
 struct MinZPending {
     bool active = false;
     hipStream_t s = nullptr;  // may be the null (default) stream
@@ -1054,15 +1051,26 @@ static ot_status hi_stream_fork(hipStream_t caller, hipStream_t* out) {
 }
 
 // The area sums and CDFs of every job (SamplePointsUniformly's two serial float64 chains, run side by side) into
-// scratch slot 17, followed by `extra` bytes for the caller, whose leading `upload` bytes travel to the device with the
-// chain table in one copy: fill(host, dev) writes them once the layout is known.  cdf[j]: the job's CDF (device);
+// the sampler workspace, followed by `extra` bytes for the caller, whose leading `upload` bytes travel to the device
+// with the chain table in one copy: fill(host, dev) writes them once the layout is known.  cdf[j]: the job's CDF (device);
 // ncum[j]: room for its rounded counts; *extra_dev: the caller's device region.
 static ot_status sample_cdfs(const ot_mesh_sample_job* jobs, int32_t n_jobs, size_t extra, size_t upload,
                              const std::function<void(char*, char*)>& fill, size_t zero_off, size_t zero_bytes,
                              hipStream_t stream, std::vector<double*>& cdf, std::vector<long long*>& ncum,
                              char** extra_dev, hipEvent_t mark = nullptr, int mark_at = 0) {
     if (g_minz.active) return fail(OT_ERR_INVALID_ARGUMENT, "[SamplePointsUniformly] an async sampling is pending");
-    size_t bytes = 256;
+    // per job: the area sum, the CDF, q = a / s, the rounded counts (+ 64 B), the chains' auxiliary arrays -- cut
+    // from what `alloc` hands out: first sized job by job, then taken from the one buffer in the same order
+    auto job_ws = [](auto&& alloc, int64_t nt) {
+        const size_t nt2 = (size_t)((nt + 1) & ~(int64_t)1);
+        return carve(alloc, Arr<double>{1}, Arr<double>{nt2}, Arr<double>{nt2}, Arr<long long>{nt2 + 8},
+                     Arr<char>{chain_aux_bytes(nt)});
+    };
+    size_t bytes = 0;
+    auto sizing = [&bytes](size_t b) {
+        bytes += carve_up(b);
+        return (void*)nullptr;
+    };
     int64_t max_nt = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const ot_mesh_sample_job& m = jobs[j];
@@ -1070,38 +1078,39 @@ static ot_status sample_cdfs(const ot_mesh_sample_job* jobs, int32_t n_jobs, siz
         if (!m.vertices || !m.triangles || !m.out_xyz || (m.out_normals && !m.vertex_normals) ||
             (m.out_colors && !m.vertex_colors) || m.n_vertices <= 0)
             return fail(OT_ERR_INVALID_ARGUMENT, "[SamplePointsUniformly] invalid arguments");
-        bytes += (size_t)m.n_triangles * 32 + 256 + chain_aux_bytes(m.n_triangles);
+        job_ws(sizing, m.n_triangles);
         max_nt = m.n_triangles > max_nt ? m.n_triangles : max_nt;
     }
     const size_t table = sizeof(ChainJob) * 2 * (size_t)n_jobs;
-    char* ws = (char*)scratch(bytes + table + extra + 512, 17);
+    char* ws = (char*)scratch(bytes + table + extra, Slot::MESH_SAMPLE_WS);  // ... the chain table, the caller's region
     if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
     // [sum chains | CDF chains | caller's upload], sent by upload_small (kernel arguments; pinned memory serves the
     // copy fallback of large tables, and the callers synchronise before returning, so the slot is free again)
-    char* up = (char*)pinned_scratch(table + upload, 0);
+    char* up = (char*)pinned_scratch(table + upload, PinnedSlot::MESH_SAMPLE_UPLOAD);
     if (!up) return fail(OT_ERR_HIP, "pinned allocation failed");
     ChainJob* chain = (ChainJob*)up;
     std::vector<double*> sums(n_jobs), qs(n_jobs);
     cdf.assign(n_jobs, nullptr);
     ncum.assign(n_jobs, nullptr);
     char* cur = ws;
+    auto bump = [&cur](size_t b) {
+        char* p = cur;
+        cur += carve_up(b);
+        return (void*)p;
+    };
     for (int j = 0; j < n_jobs; ++j) {
-        const int64_t nt = jobs[j].n_triangles, nt2 = (nt + 1) & ~(int64_t)1;
-        sums[j] = (double*)cur;
-        cdf[j] = sums[j] + 8;  // 64-B offset: 16-B aligned rows for the chains' double2 loads
-        qs[j] = cdf[j] + nt2;
-        ncum[j] = (long long*)(qs[j] + nt2);
-        cur = (char*)(ncum[j] + nt2) + 64;
-        cur = (char*)(((uintptr_t)cur + 63) & ~(uintptr_t)63);
+        const int64_t nt = jobs[j].n_triangles;
+        char* aux;
+        std::tie(sums[j], cdf[j], qs[j], ncum[j], aux) = job_ws(bump, nt);  // (rows on 256 B: the chains load double2)
         ChainJob cs{};
         cs.x = cdf[j], cs.n = nt, cs.out = sums[j];
-        cur = chain_aux(cur, nt, cs);
+        chain_aux(aux, nt, cs);
         ChainJob cc = cs;
         cc.x = qs[j], cc.out = cdf[j];  // the CDF overwrites the areas once q = a / s is formed
         chain[j] = cs;
         chain[n_jobs + j] = cc;
     }
-    ChainJob* djobs = (ChainJob*)(((uintptr_t)cur + 63) & ~(uintptr_t)63);
+    ChainJob* djobs = (ChainJob*)cur;
     *extra_dev = (char*)djobs + table;
     if (upload) fill(up + table, *extra_dev);
     // the tables (and the caller's zeroed words) land from the first areas launch when they fit its arguments
@@ -1170,7 +1179,7 @@ ot_status ot_mesh_sample_points_uniformly_after(const ot_mesh_sample_job* jobs, 
 }  // extern "C"
 
 namespace ot {
-// The fused sampler's launches (on the caller's stream); the kept counts land in pinned slot 1 once it drains.  *hs:
+// The fused sampler's launches (on the caller's stream); the kept counts land in pinned memory once it drains.  *hs:
 // the stream to wait on.
 static ot_status min_z_enqueue(const ot_mesh_sample_job* jobs, int32_t n_jobs, int64_t n_points, uint64_t seed,
                                double z_min, void* stream_, hipStream_t* hs, hipEvent_t mark = nullptr,
@@ -1208,7 +1217,7 @@ static ot_status min_z_enqueue(const ot_mesh_sample_job* jobs, int32_t n_jobs, i
         }
     };
     // the kept counts land in pinned host memory, written by each job's last tile (no read-back copy)
-    long long* kept = (long long*)pinned_scratch(sizeof(long long) * (size_t)n_jobs, 1, true);
+    long long* kept = (long long*)pinned_scratch(sizeof(long long) * (size_t)n_jobs, PinnedSlot::MESH_SAMPLE_KEPT, true);
     if (!kept) return fail(OT_ERR_HIP, "pinned allocation failed");
     for (int j = 0; j < n_jobs; ++j)
         if (jobs[j].n_triangles > 0x7FFFFFFF) return fail(OT_ERR_INVALID_ARGUMENT, "[SamplePointsUniformly] too many triangles");
@@ -1233,7 +1242,7 @@ static ot_status min_z_enqueue(const ot_mesh_sample_job* jobs, int32_t n_jobs, i
 }
 static ot_status min_z_wait(hipStream_t hs, int32_t n_jobs, int64_t* n_kept_host) {
     OT_HIP_TRY(hipStreamSynchronize(hs));  // the kept counts (written by each job's last tile)
-    const long long* kept = (const long long*)pinned_scratch(sizeof(long long) * (size_t)n_jobs, 1, true);
+    const long long* kept = (const long long*)pinned_scratch(sizeof(long long) * (size_t)n_jobs, PinnedSlot::MESH_SAMPLE_KEPT, true);
     for (int j = 0; j < n_jobs; ++j) n_kept_host[j] = kept[j];
     return OT_OK;
 }
@@ -1309,14 +1318,12 @@ ot_status ot_mesh_get_surface_area(const double* V, int64_t nv, const int32_t* T
         return OT_OK;
     }
     const int64_t nt2 = (nt + 1) & ~(int64_t)1;
-    char* ws = (char*)scratch((size_t)nt2 * 8 + chain_aux_bytes(nt) + sizeof(ChainJob) + 512, 17);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
+    auto [sum, area, aux, djob] = carve(scratch_of(Slot::MESH_SAMPLE_WS), Arr<double>{1}, Arr<double>{(size_t)nt2},
+                                        Arr<char>{chain_aux_bytes(nt)}, Arr<ChainJob>{1});
+    if (!sum) return fail(OT_ERR_HIP, "scratch allocation failed");
     ChainJob jb{};
-    double* sum = (double*)ws;
-    double* area = sum + 8;
     jb.x = area, jb.n = nt, jb.out = sum;
-    char* cur = chain_aux((char*)(area + nt2), nt, jb);
-    ChainJob* djob = (ChainJob*)cur;
+    chain_aux(aux, nt, jb);
     hipLaunchKernelGGL(k_tri_areas, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, stream, V, T, nt, area,
                        (double*)nullptr);
     OT_HIP_TRY(hipMemcpyAsync(djob, &jb, sizeof(ChainJob), hipMemcpyHostToDevice, stream));
@@ -1335,7 +1342,7 @@ ot_status otx_chain_walk_trace(const double* x, int64_t n, int32_t cdf, double* 
     hipStream_t stream = S(stream_);
     if (n <= 0 || !x || !out || !trace || cap <= 0 || ((uintptr_t)x & 15))
         return fail(OT_ERR_INVALID_ARGUMENT, "[chain] invalid arguments");
-    char* ws = (char*)scratch(chain_aux_bytes(n) + sizeof(ChainJob) + 256, 17);
+    char* ws = (char*)scratch(chain_aux_bytes(n) + sizeof(ChainJob) + 256, Slot::MESH_SAMPLE_WS);
     if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
     ChainJob jb{};
     jb.x = x, jb.n = n, jb.out = out;
@@ -1357,7 +1364,7 @@ ot_status otx_serial_chain_f64(const double* x, int64_t n, int32_t cdf, double* 
                                void* stream_) {
     hipStream_t stream = S(stream_);
     if (n <= 0 || !x || !out || ((uintptr_t)x & 15)) return fail(OT_ERR_INVALID_ARGUMENT, "[chain] invalid arguments");
-    char* ws = (char*)scratch(chain_aux_bytes(n) + sizeof(ChainJob) + 256, 17);
+    char* ws = (char*)scratch(chain_aux_bytes(n) + sizeof(ChainJob) + 256, Slot::MESH_SAMPLE_WS);
     if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
     ChainJob jb{};
     jb.x = x, jb.n = n, jb.out = out;

@@ -18,7 +18,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "grid.h"
+#include "sor.h"
 
 namespace ot {
 
@@ -342,26 +342,11 @@ static ot_status check_search(const char* who, int32_t knn, double radius) {
 // cov[n][9] of the cloud (n > 0); synchronises (grid build), the kernel itself is only queued
 static ot_status covariances(const double* xyz, int64_t n, int32_t knn, double radius, double* cov,
                              hipStream_t stream) {
+    // cells sized as SOR's (sor.h): the grid only changes speed
     double mn[3], mx[3];
-    ot_status st = bounds_host(xyz, n, stream, mn, mx);
-    if (st != OT_OK) return st;
-    // cells sized as SOR's (outlier.hip): ~sor_cell_target points per occupied cell of a surface-like cloud, refined
-    // once from the measured occupancy; the grid only changes speed
-    const double target = sor_cell_target(knn);
-    double ext[3];
-    for (int a = 0; a < 3; ++a) ext[a] = std::max(mx[a] - mn[a], 1e-9);
-    std::sort(ext, ext + 3);
-    const double hmin = ext[2] / 5.0e5;
-    double h = std::max(std::sqrt(0.5 * ext[2] * ext[1] * target / (double)n), hmin);
     GridBuild gb;
-    st = single_frame_grid(xyz, n, h, mn, mx, GRID_NBR3, stream, gb);
+    ot_status st = occupancy_grid(xyz, n, sor_cell_target(knn), GRID_NBR3, mn, mx, stream, gb);
     if (st != OT_OK) return st;
-    const double occ = (double)n / (double)std::max<int64_t>(gb.ncells, 1);
-    if (occ > 2.5 * target || occ < 0.4 * target) {
-        h = std::max(h * std::sqrt(target / occ), hmin);
-        st = single_frame_grid(xyz, n, h, mn, mx, GRID_NBR3, stream, gb);
-        if (st != OT_OK) return st;
-    }
     const double r2 = radius > 0.0 ? radius * radius : 0.0;
     const dim3 grid((unsigned)((n + 63) / 64)), block(64);
     if (knn <= 32) hipLaunchKernelGGL(k_nrm_cov<32>, grid, block, 0, stream, gb.g, xyz, n, (int)knn, r2, cov);
@@ -397,8 +382,8 @@ ot_status ot_estimate_normals(const double* xyz, int64_t n, int32_t knn, double 
     if (n <= 0) return OT_OK;
     if (!xyz || !normals_out || n > 0x7FFFFFFF) return fail(OT_ERR_INVALID_ARGUMENT, "[EstimateNormals] invalid buffers");
     double* cov = cov_out;
-    if (!cov) {  // slot 12: neither the bounds nor the grid use it
-        cov = (double*)scratch((size_t)n * 9 * sizeof(double), 12);
+    if (!cov) {
+        cov = (double*)scratch((size_t)n * 9 * sizeof(double), Slot::OP_WS);
         if (!cov) return fail(OT_ERR_HIP, "scratch allocation failed");
     }
     st = covariances(xyz, n, knn, radius, cov, stream);

@@ -1,11 +1,8 @@
 // outlier.hip — PointCloud::RemoveStatisticalOutliers / RemoveRadiusOutliers / ComputePointCloudDistance on
 // MI355X (eval_cone.py:99-110).
 //
-// Neighbour search uses a uniform cell grid (grid.h) instead of Open3D's KD-tree (the results are defined by the
-// distances, not by the search structure):
-//   grid build : (frame, cell) key per point -> stable radix sort -> cell heads -> open-addressing hash (cell key ->
-//                [start, end) in the sorted order) -> per cell the z-column ranges of its 3x3 / 5x5 block; points
-//                are re-laid out in sorted order so a cell's points are contiguous in HBM.
+// Neighbour search uses a uniform cell grid (grid.h, built by grid.hip) instead of Open3D's KD-tree (the results are
+// defined by the distances, not by the search structure):
 //   ROR        : cell = radius * ROR_CELL_SCALE (grid.h: a rounding margin, so no neighbour falls outside the
 //                block); count |{j : d2(i, j) < r^2}| over the 27 neighbour cells (exact integers).
 //   SOR        : exact k nearest neighbours: the columns of the query's block are scanned nearest-first into a
@@ -23,8 +20,7 @@
 
 #include "chain.h"
 #include "compact.h"
-#include "grid.h"
-#include "sort.h"
+#include "sor.h"
 
 namespace ot {
 
@@ -33,102 +29,6 @@ __device__ inline int64_t sor_out(const GridDev& g, int64_t j) { return g.sidx ?
 // dependent binary search over the frame offsets at the head of every query's chain)
 __device__ inline int sorted_frame(const GridDev& g, int64_t j) {
     return g.nframes > 1 ? (int)(g.pkey[j] >> g.sf) : 0;
-}
-
-template <typename KeyT>
-__global__ __launch_bounds__(256) void k_cell_keys(const double* __restrict__ xyz, int64_t n, GridDev g, KeyT* keys,
-                                                   unsigned* idx, int* err) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int f = g.nframes > 1 ? frame_of(g.foff, g.nframes, i) : 0;
-    const double* o = g.origin + 3 * f;
-    const int x = cell_coord(xyz[i * 3 + 0], o[0], g.h);
-    const int y = cell_coord(xyz[i * 3 + 1], o[1], g.h);
-    const int z = cell_coord(xyz[i * 3 + 2], o[2], g.h);
-    const bool ok = cell_valid(g, x, y, z);
-    if (!ok) *err = 1;
-    keys[i] = ok ? (KeyT)cell_key(g, f, x, y, z) : (KeyT)0;
-    idx[i] = (unsigned)i;
-}
-
-__global__ __launch_bounds__(256) void k_widen_keys(const unsigned* __restrict__ in, int64_t n,
-                                                    unsigned long long* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
-
-// per occupied cell: its range and z; a column's first cell also inserts the column (its run of cells) into the hash
-__global__ __launch_bounds__(256) void k_grid_insert(const unsigned long long* __restrict__ skeys,
-                                                     const int* __restrict__ heads, int64_t ncells, int64_t n,
-                                                     GridDev g) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c >= ncells) return;
-    const int beg = heads[c];
-    const int end = (c + 1 < ncells) ? heads[c + 1] : (int)n;
-    const unsigned long long key = skeys[beg];
-    g.crange[c] = make_int2(beg, end);
-    g.cz[c] = (int)(key & ((1ull << g.sy) - 1));
-    const unsigned long long col = key >> g.sy;
-    if (c > 0 && (skeys[heads[c - 1]] >> g.sy) == col) return;
-    // the column's cells are contiguous (cell-major keys): its end by galloping, then bisection -- a wall's column
-    // holds dozens of cells, and a probe is two dependent loads
-    int64_t lo = c, hi = ncells, step = 1;
-    while (true) {
-        const int64_t p = c + step;
-        if (p >= ncells) break;
-        if ((skeys[heads[p]] >> g.sy) != col) {
-            hi = p;
-            break;
-        }
-        lo = p;
-        step <<= 1;
-    }
-    while (hi - lo > 1) {  // colkey(lo) == col; hi == ncells or colkey(hi) != col
-        const int64_t mid = (lo + hi) >> 1;
-        if ((skeys[heads[mid]] >> g.sy) == col) lo = mid;
-        else hi = mid;
-    }
-    const int cnt = (int)(hi - c);
-    unsigned slot = (unsigned)mix64(col) & (unsigned)g.hash_mask;
-    while (true) {  // capacity >= 2 * ncells >= 2 * columns: always terminates
-        const unsigned long long old = atomicCAS(&g.hkeys[slot], KEY_EMPTY, col);
-        if (old == KEY_EMPTY) {
-            g.hval[slot] = make_int2((int)c, cnt);
-            return;
-        }
-        slot = (slot + 1) & (unsigned)g.hash_mask;
-    }
-}
-
-// One lane per (cell, column of its (2R+1)^2 neighbourhood): one column probe, then the column's cells in
-// z-R..z+R (and, R = 2, z-1..z+1 for the inner 3x3 columns) as contiguous point ranges.
-template <int R>
-__global__ __launch_bounds__(256) void k_cell_nbr(const unsigned long long* __restrict__ skeys,
-                                                  const int* __restrict__ heads, int64_t ncells, GridDev g,
-                                                  int2* __restrict__ nbr3, int2* __restrict__ nbr5) {
-    constexpr int W = 2 * R + 1, COLS = W * W;
-    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= ncells * COLS) return;
-    const int64_t c = gid / COLS;
-    const int t = (int)(gid - c * COLS);
-    const int dx = t / W - R, dy = t % W - R;
-    const unsigned long long key = skeys[heads[c]];
-    const int f = (int)(key >> g.sf);
-    const int z = (int)(key & ((1ull << g.sy) - 1));
-    const int y = (int)((key >> g.sy) & ((1ull << (g.sx - g.sy)) - 1)) + dy;
-    const int x = (int)((key >> g.sx) & ((1ull << (g.sf - g.sx)) - 1)) + dx;
-    const int2 col = grid_column(g, f, x, y);
-    if (R == 2) nbr5[c * NBR5 + t] = column_range(g, col, z - 2, z + 2);
-    if (nbr3 && dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1)
-        nbr3[c * NBR3 + (dx + 1) * 3 + (dy + 1)] = column_range(g, col, z - 1, z + 1);
-}
-
-__global__ __launch_bounds__(256) void k_gather_sorted(const double* __restrict__ xyz, const unsigned* __restrict__ sidx,
-                                                       int64_t n, double* __restrict__ sxyz) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n * 3) return;
-    const int64_t j = t / 3, a = t % 3;
-    sxyz[t] = xyz[(int64_t)sidx[j] * 3 + a];
 }
 
 // ------------------------------------------------------------------------------------------------ ROR
@@ -727,178 +627,11 @@ struct IndexEmit {
     __device__ void operator()(int64_t i, int64_t pos) const { out[pos] = i; }
 };
 
-// ------------------------------------------------------------------------------------ grid builder (host)
-static int bits_for_host(int64_t v) {  // bits to represent 0..v
-    int b = 1;
-    while (b < 62 && (v >> b) != 0) ++b;
-    return b;
-}
-
-ot_status build_grid_frames(const double* xyz, int64_t n, int nframes, const int* d_foff, const double* d_origin,
-                            double h, const int dims[3], int nbr, hipStream_t stream, GridBuild& out, int slot0,
-                            const int* h_foff) {
-    GridDev& g = out.g;
-    g.h = h;
-    g.origin = d_origin;
-    g.foff = d_foff;
-    g.nframes = nframes;
-    int bits[3];
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1 || dims[a] > 1000000)
-            return fail(OT_ERR_INVALID_ARGUMENT, "neighbour grid out of range (radius too small for the extent)");
-        g.dim[a] = dims[a];
-        bits[a] = bits_for_host(g.dim[a] - 1);
-    }
-    g.sy = bits[2];
-    g.sx = bits[1] + bits[2];
-    g.sf = bits[0] + bits[1] + bits[2];
-    const int end_bit = g.sf + (nframes > 1 ? bits_for_host(nframes - 1) : 0);
-    if (end_bit > 64) return fail(OT_ERR_INVALID_ARGUMENT, "neighbour grid keys exceed 64 bits");
-    char* ws = (char*)scratch(256 + (size_t)n * (8 + 8 + 4 + 4 + 4 + 4 + 24), slot0);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    int* err = (int*)ws;
-    unsigned long long* kin = (unsigned long long*)(ws + 256);
-    unsigned long long* kout = kin + n;
-    unsigned* vin = (unsigned*)(kout + n);
-    unsigned* vout = vin + n;
-    int* heads = (int*)(vout + n);
-    int* pcell = heads + n;
-    double* sxyz = (double*)(((uintptr_t)(pcell + n) + 15) & ~(uintptr_t)15);
-    OT_HIP_TRY(hipMemsetAsync(err, 0, sizeof(int), stream));
-    ot_status st;
-    if (end_bit <= 32 && n > (int64_t)(1 << 21)) {  // large sorts on 32-bit keys: 8 B per pair per pass, not 12
-        unsigned* k32 = (unsigned*)kin;
-        unsigned* k32o = k32 + n;
-        hipLaunchKernelGGL(k_cell_keys<unsigned>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, xyz, n, g,
-                           k32, vin, err);
-        OT_LAUNCH_CHECK();
-        if (h_foff && nframes > 1 && nframes <= 64) {  // frames are contiguous: sort each on its cell bits alone
-            std::vector<int64_t> seg((size_t)nframes + 1);
-            for (int f = 0; f <= nframes; ++f) seg[f] = h_foff[f];
-            st = sort_segments_u32_u32(k32, k32o, vin, vout, seg.data(), nframes, std::max(g.sf, 1), stream, 3);
-        } else {
-            st = sort_pairs_u32_u32(k32, k32o, vin, vout, (size_t)n, std::max(end_bit, 1), stream, 3);
-        }
-        if (st != OT_OK) return st;
-        hipLaunchKernelGGL(k_widen_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const unsigned*)k32o,
-                           n, kout);
-    } else {
-        hipLaunchKernelGGL(k_cell_keys<unsigned long long>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                           xyz, n, g, kin, vin, err);
-        OT_LAUNCH_CHECK();
-        st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, std::max(end_bit, 1), stream, 3);
-        if (st != OT_OK) return st;
-    }
-    int64_t ncells = 0;
-    st = compact_segments(n, kout, heads, pcell, stream, &ncells, slot0 + 1);  // synchronises
-    if (st != OT_OK) return st;
-    int e = 0;
-    OT_HIP_TRY(hipMemcpyAsync(&e, err, sizeof(int), hipMemcpyDeviceToHost, stream));
-    OT_HIP_TRY(hipStreamSynchronize(stream));
-    if (e) return fail(OT_ERR_INVALID_ARGUMENT, "neighbour grid out of range (non-finite point coordinates)");
-    int64_t cap = 1;
-    while (cap < 2 * ncells + 2) cap <<= 1;
-    const bool w3 = nbr & GRID_NBR3, w5 = nbr & GRID_NBR5;
-    const size_t per_cell = (w3 ? NBR3 * 8 : 0) + (w5 ? NBR5 * 8 : 0) + 12;
-    char* hs = (char*)scratch((size_t)cap * (8 + 8) + (size_t)ncells * per_cell + 128, slot0 + 2);
-    if (!hs) return fail(OT_ERR_HIP, "scratch allocation failed");
-    g.hkeys = (unsigned long long*)hs;
-    g.hval = (int2*)(g.hkeys + cap);
-    int2* cur = g.hval + cap;
-    int2* nbr3 = w3 ? cur : nullptr;
-    cur += w3 ? ncells * NBR3 : 0;
-    int2* nbr5 = w5 ? cur : nullptr;
-    cur += w5 ? ncells * NBR5 : 0;
-    g.crange = cur;
-    g.cz = (int*)(g.crange + ncells);
-    g.hash_mask = (int)(cap - 1);
-    OT_HIP_TRY(hipMemsetAsync(g.hkeys, 0xFF, sizeof(unsigned long long) * cap, stream));
-    hipLaunchKernelGGL(k_grid_insert, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, stream, kout, heads,
-                       ncells, n, g);  // cell ranges / z and the column hash, read by k_cell_nbr
-    if (w5)
-        hipLaunchKernelGGL(k_cell_nbr<2>, dim3((unsigned)((ncells * NBR5 + 255) / 256)), dim3(256), 0, stream, kout,
-                           heads, ncells, g, nbr3, nbr5);
-    else if (w3)
-        hipLaunchKernelGGL(k_cell_nbr<1>, dim3((unsigned)((ncells * NBR3 + 255) / 256)), dim3(256), 0, stream, kout,
-                           heads, ncells, g, nbr3, nbr5);
-    hipLaunchKernelGGL(k_gather_sorted, dim3((unsigned)((n * 3 + 255) / 256)), dim3(256), 0, stream, xyz, vout, n, sxyz);
-    OT_LAUNCH_CHECK();
-    g.sxyz = sxyz;
-    g.sidx = vout;
-    g.pkey = kout;
-    g.pcell = pcell;
-    g.nbr3 = nbr3;
-    g.nbr5 = nbr5;
-    out.ncells = ncells;
-    return OT_OK;
-}
-
-ot_status build_grid_sorted(const double* xyz, const unsigned long long* ckeys, int64_t n, int nframes,
-                            const int* d_foff, const double* d_origin, double h, const int bits[3], int nbr,
-                            hipStream_t stream, GridBuild& out, int slot0) {
-    GridDev& g = out.g;
-    g.h = h;
-    g.origin = d_origin;
-    g.foff = d_foff;
-    g.nframes = nframes;
-    for (int a = 0; a < 3; ++a) {
-        if (bits[a] < 0 || bits[a] > 20)
-            return fail(OT_ERR_INVALID_ARGUMENT, "neighbour grid out of range (radius too small for the extent)");
-        g.dim[a] = 1 << bits[a];
-    }
-    g.sy = bits[2];
-    g.sx = bits[1] + bits[2];
-    g.sf = bits[0] + bits[1] + bits[2];
-    char* ws = (char*)scratch(256 + (size_t)n * 8, slot0);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    int* heads = (int*)ws;
-    int* pcell = heads + n;
-    int64_t ncells = 0;
-    ot_status st = compact_segments(n, ckeys, heads, pcell, stream, &ncells, slot0 + 1);  // synchronises
-    if (st != OT_OK) return st;
-    int64_t cap = 1;
-    while (cap < 2 * ncells + 2) cap <<= 1;
-    const bool w3 = nbr & GRID_NBR3, w5 = nbr & GRID_NBR5;
-    const size_t per_cell = (w3 ? NBR3 * 8 : 0) + (w5 ? NBR5 * 8 : 0) + 12;
-    char* hs = (char*)scratch((size_t)cap * (8 + 8) + (size_t)ncells * per_cell + 128, slot0 + 2);
-    if (!hs) return fail(OT_ERR_HIP, "scratch allocation failed");
-    g.hkeys = (unsigned long long*)hs;
-    g.hval = (int2*)(g.hkeys + cap);
-    int2* cur = g.hval + cap;
-    int2* nbr3 = w3 ? cur : nullptr;
-    cur += w3 ? ncells * NBR3 : 0;
-    int2* nbr5 = w5 ? cur : nullptr;
-    cur += w5 ? ncells * NBR5 : 0;
-    g.crange = cur;
-    g.cz = (int*)(g.crange + ncells);
-    g.hash_mask = (int)(cap - 1);
-    OT_HIP_TRY(hipMemsetAsync(g.hkeys, 0xFF, sizeof(unsigned long long) * cap, stream));
-    if (ncells > 0) {
-        hipLaunchKernelGGL(k_grid_insert, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, stream, ckeys, heads,
-                           ncells, n, g);
-        if (w5)
-            hipLaunchKernelGGL(k_cell_nbr<2>, dim3((unsigned)((ncells * NBR5 + 255) / 256)), dim3(256), 0, stream,
-                               ckeys, heads, ncells, g, nbr3, nbr5);
-        else if (w3)
-            hipLaunchKernelGGL(k_cell_nbr<1>, dim3((unsigned)((ncells * NBR3 + 255) / 256)), dim3(256), 0, stream,
-                               ckeys, heads, ncells, g, nbr3, nbr5);
-        OT_LAUNCH_CHECK();
-    }
-    g.sxyz = xyz;
-    g.sidx = nullptr;
-    g.pkey = ckeys;
-    g.pcell = pcell;
-    g.nbr3 = nbr3;
-    g.nbr5 = nbr5;
-    out.ncells = ncells;
-    return OT_OK;
-}
-
 // test hook otx_sor_netfill: 0 = the sequential fill of the stage-1 list (A/B timing and parity of the network fill)
 static bool g_sor_netfill = true;
 
 ot_status sor_frames(const GridBuild& gb, int64_t n, const int* h_foff, int nb_neighbors, double std_ratio,
-                     double* avg, double* stats, hipStream_t stream, int slot0) {
+                     double* avg, double* stats, hipStream_t stream, const SorSlots& slots) {
     const int F = gb.g.nframes;
     int64_t max_n = 0;
     for (int f = 0; f < F; ++f) max_n = std::max<int64_t>(max_n, h_foff[f + 1] - h_foff[f]);
@@ -908,18 +641,19 @@ ot_status sor_frames(const GridBuild& gb, int64_t n, const int* h_foff, int nb_n
     const int km = kk <= 4 ? 4 : kk <= 8 ? 8 : kk <= 12 ? 12 : kk <= 16 ? 16 : kk <= 20 ? 20 : kk <= 24 ? 24
                  : kk <= 32 ? 32 : kk <= 48 ? 48 : 64;
     // and of stage-2 misses (stage 3, one wave each): their pending slots (capacity n; count and list stay in place)
-    const size_t per = 4 + 8 + 8 * (size_t)km;
-    char* pw = (char*)scratch((size_t)n * (per + 4) + 1024, slot0 + 1);
-    if (!pw) return fail(OT_ERR_HIP, "scratch allocation failed");
+    const size_t un = (size_t)n;
+    auto [counts, j2, have2, best2, j3] = carve(scratch_of(slots.pending), Arr<int>{2}, Arr<int>{un},
+                                                Arr<long long>{un}, Arr<double>{(size_t)km * un}, Arr<int>{un});
+    if (!counts) return fail(OT_ERR_HIP, "scratch allocation failed");
     SorPend pd, pd3;
-    pd.count = (int*)pw;
+    pd.count = counts;  // {stage 2's, stage 3's}: zeroed by one memset
     pd3.count = pd.count + 1;
-    pd.j = (int*)(pw + 256);
-    pd.have = (long long*)(((uintptr_t)(pd.j + n) + 15) & ~(uintptr_t)15);
-    pd.best = (double*)(pd.have + n);
+    pd.j = j2;
+    pd.have = have2;
+    pd.best = best2;
     pd.cap = n;
-    pd3.j = (int*)(((uintptr_t)(pd.best + (size_t)km * n) + 255) & ~(uintptr_t)255);
-    pd3.have = nullptr;  // in the stage-2 slot (pd)
+    pd3.j = j3;
+    pd3.have = nullptr;  // aliased on purpose: stage 3 reads a query's count and list in its stage-2 entry (pd)
     pd3.best = nullptr;
     pd3.cap = n;
     OT_HIP_TRY(hipMemsetAsync(pd.count, 0, 2 * sizeof(int), stream));
@@ -948,26 +682,21 @@ ot_status sor_frames(const GridBuild& gb, int64_t n, const int* h_foff, int nb_n
     else OT_SOR_LAUNCH(64);
 #undef OT_SOR_LAUNCH
     OT_LAUNCH_CHECK();
-    return sor_stats_frames(avg, gb.g.foff, h_foff, F, std_ratio, stats, stream, slot0);
+    return sor_stats_frames(avg, gb.g.foff, h_foff, F, std_ratio, stats, stream, slots.stats);
 }
 
 ot_status sor_stats_frames(const double* avg, const int* d_foff, const int* h_foff, int F, double std_ratio,
-                           double* stats, hipStream_t stream, int slot) {
+                           double* stats, hipStream_t stream, Slot slot) {
     int64_t max_n = 0;
     for (int f = 0; f < F; ++f) max_n = std::max<int64_t>(max_n, h_foff[f + 1] - h_foff[f]);
     const int64_t n = h_foff[F];
-    const int slot0 = slot;
     // the two sequential float64 sums per frame (exact chains): x values, chain jobs, valid counts, sums
     const int nvb = (int)std::max<int64_t>((max_n + 255) / 256, 1);
     size_t aux = 0;
     for (int f = 0; f < F; ++f) aux += chain_aux_bytes(h_foff[f + 1] - h_foff[f]);
-    const size_t bytes = (size_t)n * 8 + 256 + aux + (sizeof(ChainJob) + 32) * (size_t)F + (size_t)F * nvb * 4 + 512;
-    char* ws = (char*)scratch(bytes, slot0);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    double* x = (double*)ws;
-    double* sums = (double*)(((uintptr_t)(x + n) + 63) & ~(uintptr_t)63);
-    int* vpart = (int*)(sums + F);
-    char* cur = (char*)(((uintptr_t)(vpart + (size_t)F * nvb) + 63) & ~(uintptr_t)63);
+    auto [x, sums, vpart, cur, jobs_dev] =
+        sor_stats_ws(scratch_of(slot), (size_t)n, (size_t)F, (size_t)nvb, aux, sizeof(ChainJob));
+    if (!x) return fail(OT_ERR_HIP, "scratch allocation failed");
     std::vector<ChainJob> jobs((size_t)F);
     for (int f = 0; f < F; ++f) {
         ChainJob& jb = jobs[f];
@@ -976,7 +705,7 @@ ot_status sor_stats_frames(const double* avg, const int* d_foff, const int* h_fo
         jb.out = sums + f;
         cur = chain_aux(cur, jb.n, jb);
     }
-    ChainJob* djobs = (ChainJob*)cur;
+    ChainJob* djobs = (ChainJob*)jobs_dev;
     OT_HIP_TRY(hipMemcpyAsync(djobs, jobs.data(), sizeof(ChainJob) * F, hipMemcpyHostToDevice, stream));
     const dim3 vgrid((unsigned)nvb, (unsigned)F);
     hipLaunchKernelGGL(k_sor_values, vgrid, dim3(256), 0, stream, (const double*)avg, d_foff, 0,
@@ -997,65 +726,6 @@ ot_status sor_stats_frames(const double* avg, const int* d_foff, const int* h_fo
 }  // namespace ot
 
 using namespace ot;
-
-ot_status ot::bounds_host(const double* xyz, int64_t n, hipStream_t stream, double mn[3], double mx[3]) {
-    Bounds* b = (Bounds*)scratch(sizeof(Bounds) + 64, 11);
-    if (!b) return fail(OT_ERR_HIP, "scratch allocation failed");
-    unsigned long long* part = (unsigned long long*)scratch(sizeof(unsigned long long) * BOUNDS_BLOCKS * 6, 19);
-    if (!part) return fail(OT_ERR_HIP, "scratch allocation failed");
-    launch_bounds(xyz, n, b, part, stream);
-    OT_LAUNCH_CHECK();
-    Bounds hb;
-    OT_HIP_TRY(hipMemcpyAsync(&hb, b, sizeof(Bounds), hipMemcpyDeviceToHost, stream));
-    OT_HIP_TRY(hipStreamSynchronize(stream));
-    for (int a = 0; a < 3; ++a) {
-        mn[a] = ordered_to_dbl(hb.mn[a]);
-        mx[a] = ordered_to_dbl(hb.mx[a]);
-    }
-    return OT_OK;
-}
-
-// one frame: origin = the cloud's minimum corner, cells per axis from the extent.  frame_dev receives the device
-// origin [3] and offsets {0, n} (scratch slot 20).
-ot_status ot::single_frame_grid(const double* xyz, int64_t n, double h, const double mn[3], const double mx[3],
-                                   int nbr, hipStream_t stream, GridBuild& gb) {
-    int dims[3];
-    for (int a = 0; a < 3; ++a) {
-        const double span = std::floor((mx[a] - mn[a]) / h);
-        if (!(span < 1.0e6)) return fail(OT_ERR_INVALID_ARGUMENT, "neighbour grid out of range (radius too small for the extent)");
-        dims[a] = (int)span + 1;
-    }
-    char* fr = (char*)scratch(64, 20);
-    if (!fr) return fail(OT_ERR_HIP, "scratch allocation failed");
-    const double org[4] = {mn[0], mn[1], mn[2], 0.0};
-    const int off[2] = {0, (int)n};
-    OT_HIP_TRY(hipMemcpyAsync(fr, org, sizeof(org), hipMemcpyHostToDevice, stream));
-    OT_HIP_TRY(hipMemcpyAsync(fr + 32, off, sizeof(off), hipMemcpyHostToDevice, stream));
-    // build_grid_frames synchronises the stream before returning, so org / off outlive their copies
-    return build_grid_frames(xyz, n, 1, (const int*)(fr + 32), (const double*)fr, h, dims, nbr, stream, gb, 22);
-}
-
-ot_status ot::nn_target_grid(const double* tgt, int64_t m, int nbr, hipStream_t stream, double mn[3], double mx[3],
-                             GridBuild& gb) {
-    ot_status st = bounds_host(tgt, m, stream, mn, mx);
-    if (st != OT_OK) return st;
-    // ~4 target points per occupied cell of a surface-like cloud (the grid only changes speed)
-    double ext[3];
-    for (int a = 0; a < 3; ++a) ext[a] = std::max(mx[a] - mn[a], 1e-9);
-    std::sort(ext, ext + 3);
-    const double target = 4.0;
-    const double hmin = ext[2] / 5.0e5;
-    double h = std::max(std::sqrt(0.5 * ext[2] * ext[1] * target / (double)m), hmin);
-    st = single_frame_grid(tgt, m, h, mn, mx, nbr, stream, gb);
-    if (st != OT_OK) return st;
-    const double occ = (double)m / (double)std::max<int64_t>(gb.ncells, 1);
-    if (occ > 2.5 * target || occ < 0.4 * target) {
-        h = std::max(h * std::sqrt(target / occ), hmin);
-        st = single_frame_grid(tgt, m, h, mn, mx, nbr, stream, gb);
-        if (st != OT_OK) return st;
-    }
-    return OT_OK;
-}
 
 extern "C" {
 // test / diagnostic hook (not part of the drop-in boundary): 1 (default) = stage 1 fills its list with the own
@@ -1084,12 +754,12 @@ ot_status ot_remove_radius_outlier(const double* xyz, int64_t n, int32_t nb_poin
     GridBuild gb;
     st = single_frame_grid(xyz, n, radius * ROR_CELL_SCALE, mn, mx, GRID_NBR3, stream, gb);
     if (st != OT_OK) return st;
-    unsigned char* keep = (unsigned char*)scratch((size_t)n + 64, 12);
+    unsigned char* keep = (unsigned char*)scratch((size_t)n + 64, Slot::OP_WS);
     if (!keep) return fail(OT_ERR_HIP, "scratch allocation failed");
     hipLaunchKernelGGL(k_ror, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, gb.g, n, radius * radius,
                        (int)nb_points, keep);
     OT_LAUNCH_CHECK();
-    return compact(n, RorPred{keep}, IndexEmit{out_indices}, stream, n_kept_host, 13);
+    return compact(n, RorPred{keep}, IndexEmit{out_indices}, stream, n_kept_host, Slot::OP_COMPACT);
 }
 
 ot_status ot_remove_statistical_outlier(const double* xyz, int64_t n, int32_t nb_neighbors, double std_ratio,
@@ -1107,34 +777,17 @@ ot_status ot_remove_statistical_outlier(const double* xyz, int64_t n, int32_t nb
     if (!xyz || !out_indices || n > 0x7FFFFFFF)
         return fail(OT_ERR_INVALID_ARGUMENT, "[RemoveStatisticalOutliers] invalid buffers");
     double mn[3], mx[3];
-    ot_status st = bounds_host(xyz, n, stream, mn, mx);
-    if (st != OT_OK) return st;
-    // Cell size: the grid only changes speed, never the result.  Aim for ~target points per occupied cell of a
-    // surface-like cloud.  First guess: the points cover half of the bounding box's largest face; refined once from
-    // the measured occupancy (2-D scaling) when it is off by more than 2.5x.
-    const double target = sor_cell_target(nb_neighbors);
-    double ext[3];
-    for (int a = 0; a < 3; ++a) ext[a] = std::max(mx[a] - mn[a], 1e-9);
-    std::sort(ext, ext + 3);
-    const double hmin = ext[2] / 5.0e5;
-    double h = std::max(std::sqrt(0.5 * ext[2] * ext[1] * target / (double)n), hmin);
     GridBuild gb;
-    st = single_frame_grid(xyz, n, h, mn, mx, SOR_GRID_NBR, stream, gb);
+    ot_status st = occupancy_grid(xyz, n, sor_cell_target(nb_neighbors), SOR_GRID_NBR, mn, mx, stream, gb);
     if (st != OT_OK) return st;
-    const double occ = (double)n / (double)std::max<int64_t>(gb.ncells, 1);
-    if (occ > 2.5 * target || occ < 0.4 * target) {
-        h = std::max(h * std::sqrt(target / occ), hmin);
-        st = single_frame_grid(xyz, n, h, mn, mx, SOR_GRID_NBR, stream, gb);
-        if (st != OT_OK) return st;
-    }
-    char* ws = (char*)scratch((size_t)n * 8 + 256, 12);
+    char* ws = (char*)scratch((size_t)n * 8 + 256, Slot::OP_WS);
     if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
     double* stats = (double*)ws;  // [mean, std, valid, threshold]
     double* avg = out_avg_dist ? out_avg_dist : (double*)(ws + 256);
     const int foff[2] = {0, (int)n};
-    st = sor_frames(gb, n, foff, nb_neighbors, std_ratio, avg, stats, stream, 41);
+    st = sor_frames(gb, n, foff, nb_neighbors, std_ratio, avg, stats, stream, CLOUD_SOR_SLOTS);
     if (st != OT_OK) return st;
-    return compact(n, SorKeep{avg, stats, gb.g.foff, 1}, IndexEmit{out_indices}, stream, n_kept_host, 13);
+    return compact(n, SorKeep{avg, stats, gb.g.foff, 1}, IndexEmit{out_indices}, stream, n_kept_host, Slot::OP_COMPACT);
 }
 
 ot_status ot_compute_point_cloud_distance(const double* src, int64_t n, const double* tgt, int64_t m, double* out,

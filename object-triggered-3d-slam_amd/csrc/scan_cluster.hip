@@ -631,8 +631,6 @@ static ot_status set_dynamic_lds(const void* kernel, size_t bytes, std::atomic<b
 
 using namespace ot;
 
-constexpr int SLOT_CS = 60, SLOT_POSE = 61, SLOT_RAW = 62, SLOT_POS = 63, SLOT_COUNTS = 64, SLOT_OFF = 65,
-              SLOT_COMPACT = 66;
 
 extern "C" {
 
@@ -667,12 +665,12 @@ ot_status ot_scan_cluster(const float* ranges, int32_t n_scans, int32_t n_beams,
     pose_rows(poses_host, n_scans, hp);
     const float r_use = range_max * params->max_range_ratio;  // :153, float
     const int blocks = std::min<int>(n_scans, SC_MAX_BLOCKS);
-    float2* dcs = (float2*)scratch(sizeof(float2) * cs.size() + 64, SLOT_CS);
-    PoseM* dp = (PoseM*)scratch(sizeof(PoseM) * hp.size() + 64, SLOT_POSE);
-    Raw* raw = (Raw*)scratch(sizeof(Raw) * (size_t)blocks * n_beams + 64, SLOT_RAW);
-    int32_t* pos = (int32_t*)scratch(sizeof(int32_t) * (size_t)nt + 64, SLOT_POS);
-    int32_t* counts = (int32_t*)scratch(sizeof(int32_t) * 3 * (size_t)n_scans + 64, SLOT_COUNTS);
-    int64_t* doff = (int64_t*)scratch(sizeof(int64_t) * 3 * ((size_t)n_scans + 1) + 64, SLOT_OFF);
+    float2* dcs = (float2*)scratch(sizeof(float2) * cs.size() + 64, Slot::SCAN_CS);
+    PoseM* dp = (PoseM*)scratch(sizeof(PoseM) * hp.size() + 64, Slot::SCAN_POSE);
+    Raw* raw = (Raw*)scratch(sizeof(Raw) * (size_t)blocks * n_beams + 64, Slot::SCAN_RAW);
+    int32_t* pos = (int32_t*)scratch(sizeof(int32_t) * (size_t)nt + 64, Slot::SCAN_POS);
+    int32_t* counts = (int32_t*)scratch(sizeof(int32_t) * 3 * (size_t)n_scans + 64, Slot::SCAN_COUNTS);
+    int64_t* doff = (int64_t*)scratch(sizeof(int64_t) * 3 * ((size_t)n_scans + 1) + 64, Slot::SCAN_OFFSETS);
     if (!dcs || !dp || !raw || !pos || !counts || !doff) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemcpyAsync(dcs, cs.data(), sizeof(float2) * cs.size(), hipMemcpyHostToDevice, stream));
     OT_HIP_TRY(hipMemcpyAsync(dp, hp.data(), sizeof(PoseM) * (size_t)n_scans, hipMemcpyHostToDevice, stream));
@@ -737,10 +735,10 @@ ot_status ot_object_map_filter(const float* object_xyz, const int64_t* offsets_h
         const double yaw = std::atan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz));  // :166
         hp[b] = ScanPose{p[0], p[1], std::cos(yaw), std::sin(yaw)};
     }
-    float2* dcs = (float2*)scratch(sizeof(float2) * cs.size() + 64, SLOT_CS);
-    ScanPose* dp = (ScanPose*)scratch(sizeof(ScanPose) * hp.size() + 64, SLOT_POSE);
-    int32_t* kept = (int32_t*)scratch(sizeof(int32_t) * (size_t)n_scans + 64, SLOT_COUNTS);
-    int64_t* doff = (int64_t*)scratch(sizeof(int64_t) * ((size_t)n_scans + 1) + 64, SLOT_OFF);
+    float2* dcs = (float2*)scratch(sizeof(float2) * cs.size() + 64, Slot::SCAN_CS);
+    ScanPose* dp = (ScanPose*)scratch(sizeof(ScanPose) * hp.size() + 64, Slot::SCAN_POSE);
+    int32_t* kept = (int32_t*)scratch(sizeof(int32_t) * (size_t)n_scans + 64, Slot::SCAN_COUNTS);
+    int64_t* doff = (int64_t*)scratch(sizeof(int64_t) * ((size_t)n_scans + 1) + 64, Slot::SCAN_OFFSETS);
     if (!dcs || !dp || !kept || !doff) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemcpyAsync(dcs, cs.data(), sizeof(float2) * cs.size(), hipMemcpyHostToDevice, stream));
     OT_HIP_TRY(hipMemcpyAsync(dp, hp.data(), sizeof(ScanPose) * hp.size(), hipMemcpyHostToDevice, stream));
@@ -752,7 +750,7 @@ ot_status ot_object_map_filter(const float* object_xyz, const int64_t* offsets_h
                        (const ScanPose*)dp, proximity_threshold * proximity_threshold, keep_mask, kept);
     OT_LAUNCH_CHECK();
     int64_t n_kept = 0;
-    ot_status st = compact(total, MaskPred{keep_mask}, Row3Emit{object_xyz, out_xyz}, stream, &n_kept, SLOT_COMPACT);
+    ot_status st = compact(total, MaskPred{keep_mask}, Row3Emit{object_xyz, out_xyz}, stream, &n_kept, Slot::SCAN_COMPACT);
     if (st != OT_OK) return st;
     std::vector<int32_t> hk((size_t)n_scans);
     OT_HIP_TRY(hipMemcpyAsync(hk.data(), kept, sizeof(int32_t) * hk.size(), hipMemcpyDeviceToHost, stream));
@@ -785,10 +783,10 @@ ot_status ot_cluster_observations(const float* points, int32_t point_stride, con
     pose_rows(poses_host, n_clouds, hp);
     const int cap = (int)most;
     const int blocks = std::min<int>(n_clouds, SC_MAX_BLOCKS);
-    PoseM* dp = (PoseM*)scratch(sizeof(PoseM) * hp.size() + 64, SLOT_POSE);
-    Raw* raw = (Raw*)scratch(sizeof(Raw) * (size_t)blocks * cap + 64, SLOT_RAW);
-    int32_t* counts = (int32_t*)scratch(sizeof(int32_t) * (size_t)n_clouds + 64, SLOT_COUNTS);
-    int64_t* doff = (int64_t*)scratch(sizeof(int64_t) * ((size_t)n_clouds + 1) + 64, SLOT_OFF);
+    PoseM* dp = (PoseM*)scratch(sizeof(PoseM) * hp.size() + 64, Slot::SCAN_POSE);
+    Raw* raw = (Raw*)scratch(sizeof(Raw) * (size_t)blocks * cap + 64, Slot::SCAN_RAW);
+    int32_t* counts = (int32_t*)scratch(sizeof(int32_t) * (size_t)n_clouds + 64, Slot::SCAN_COUNTS);
+    int64_t* doff = (int64_t*)scratch(sizeof(int64_t) * ((size_t)n_clouds + 1) + 64, Slot::SCAN_OFFSETS);
     if (!dp || !raw || !counts || !doff) return fail(OT_ERR_HIP, "scratch allocation failed");
     OT_HIP_TRY(hipMemcpyAsync(dp, hp.data(), sizeof(PoseM) * (size_t)n_clouds, hipMemcpyHostToDevice, stream));
     OT_HIP_TRY(hipMemcpyAsync(doff, offsets_host, sizeof(int64_t) * ((size_t)n_clouds + 1), hipMemcpyHostToDevice,

@@ -43,8 +43,6 @@ constexpr unsigned SP_ZERO = 0x80000000u;  // counter bit: the candidate is the 
 // a lane gives up after this many draws (N >= ransac_n distinct indices exist, so a draw is new with probability
 // >= 1 / N; for the worst case N = 3 the chance of getting here is (2/3)^65536): the candidate is then a zero plane
 constexpr unsigned long long SP_DRAW_CAP = 1ull << 16;
-// scratch slots (the compaction holds 13; ICP 50-53, the scan clustering 60-66, the mesh components 70-72)
-constexpr int SP_SLOT_CAND = 80, SP_SLOT_TIE = 81, SP_SLOT_FINAL = 82, SP_SLOT_MAIL = 83;
 
 struct Plane4 {
     double v[4];
@@ -309,11 +307,11 @@ static ot_status segment_plane_run(const double* xyz, int64_t n, double thr, int
     std::vector<SpHolder> holders;  // the evaluated candidates that hold best_k, in iteration order
     const clk::time_point t_loop = clk::now();
     if (num_iterations > 0) {
-        char* cw = (char*)scratch((size_t)chunk * 36 + 256, SP_SLOT_CAND);
-        unsigned* mail = (unsigned*)pinned_scratch(sizeof(unsigned) * ((size_t)chunk * 9 + 2), SP_SLOT_MAIL, true);
-        if (!cw || !mail) return fail(OT_ERR_HIP, "scratch allocation failed");
-        double* planes = (double*)cw;
-        unsigned* counts = (unsigned*)(planes + (size_t)chunk * 4);
+        auto [planes, counts] =
+            carve(scratch_of(Slot::SP_CANDIDATES), Arr<double>{(size_t)chunk * 4}, Arr<unsigned>{(size_t)chunk});
+        unsigned* mail =
+            (unsigned*)pinned_scratch(sizeof(unsigned) * ((size_t)chunk * 9 + 2), PinnedSlot::SP_MAIL, true);
+        if (!planes || !mail) return fail(OT_ERR_HIP, "scratch allocation failed");
         mail[chunk * 9] = 0;  // below every sequence number sent (nothing of an earlier call is in flight)
         const unsigned tiles = (unsigned)((n + SP_TILE - 1) / SP_TILE);
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -381,11 +379,9 @@ static ot_status segment_plane_run(const double* xyz, int64_t n, double thr, int
         best = holders[0].pl;
     } else if (holders.size() > 1) {
         const int64_t stride = (n + 1) & ~(int64_t)1;
-        const size_t arr = sizeof(double) * (size_t)stride * SP_TIE_JOBS;
-        char* tw = (char*)scratch(arr + sp_chain_ws_bytes(n, SP_TIE_JOBS) + 256, SP_SLOT_TIE);
-        if (!tw) return fail(OT_ERR_HIP, "scratch allocation failed");
-        double* masked = (double*)tw;
-        char* ws = (char*)(((uintptr_t)(tw + arr) + 63) & ~(uintptr_t)63);
+        auto [masked, ws] = carve(scratch_of(Slot::SP_TIES), Arr<double>{(size_t)stride * SP_TIE_JOBS},
+                                  Arr<char>{sp_chain_ws_bytes(n, SP_TIE_JOBS)});
+        if (!masked) return fail(OT_ERR_HIP, "scratch allocation failed");
         const double root_k = std::sqrt((double)best_k);
         double best_rmse = 0.0;
         for (size_t h0 = 0; h0 < holders.size(); h0 += SP_TIE_JOBS) {
@@ -418,13 +414,10 @@ static ot_status segment_plane_run(const double* xyz, int64_t n, double thr, int
     const bool best_zero = best.v[0] == 0.0 && best.v[1] == 0.0 && best.v[2] == 0.0 && best.v[3] == 0.0;
     if (!best_zero) {
         const int64_t stride = (n + 1) & ~(int64_t)1;
-        const size_t arr = sizeof(double) * (size_t)stride * 9;
-        char* fw = (char*)scratch(arr + sp_chain_ws_bytes(n, 6) + 256, SP_SLOT_FINAL);
-        if (!fw) return fail(OT_ERR_HIP, "scratch allocation failed");
-        double* g = (double*)fw;
-        double* prod = g + 3 * stride;
-        char* ws = (char*)(((uintptr_t)(fw + arr) + 63) & ~(uintptr_t)63);
-        ot_status st = compact(n, SpPred{xyz, best, thr}, SpEmit{xyz, inliers, g, stride}, stream, &k, 13);
+        auto [g, prod, ws] = carve(scratch_of(Slot::SP_FINAL), Arr<double>{(size_t)stride * 3},
+                                   Arr<double>{(size_t)stride * 6}, Arr<char>{sp_chain_ws_bytes(n, 6)});
+        if (!g) return fail(OT_ERR_HIP, "scratch allocation failed");
+        ot_status st = compact(n, SpPred{xyz, best, thr}, SpEmit{xyz, inliers, g, stride}, stream, &k, Slot::OP_COMPACT);
         if (st != OT_OK) return st;
         if (k > 0) {
             st = sp_chain_sums(g, stride, k, 3, ws, sums, stream);

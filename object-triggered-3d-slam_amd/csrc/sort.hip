@@ -287,7 +287,7 @@ __global__ __launch_bounds__(Rs<D>::THREADS) void k_rs_scatter(const KeyT* __res
 // the own sort over segments (host segment offsets seg[0..nseg], seg[0] = 0, seg[nseg] = n)
 template <typename KeyT, int RS_ITEMS, int D>
 static ot_status rs_sort(const KeyT* kin, KeyT* kout, const unsigned* vin, unsigned* vout, const int64_t* seg, int nseg,
-                         int end_bit, hipStream_t stream, int scratch_slot, const int* dlen = nullptr) {
+                         int end_bit, hipStream_t stream, Slot scratch_slot, const int* dlen = nullptr) {
     constexpr int RS_THREADS = Rs<D>::THREADS, RS_BINS = Rs<D>::BINS;
     constexpr int RS_TILE = RS_THREADS * RS_ITEMS;
     const size_t n = (size_t)seg[nseg];
@@ -349,7 +349,7 @@ static ot_status rs_sort(const KeyT* kin, KeyT* kout, const unsigned* vin, unsig
 }
 
 ot_status sort_pairs_u64_u32(const unsigned long long* kin, unsigned long long* kout, const unsigned* vin,
-                             unsigned* vout, size_t n, int end_bit, hipStream_t stream, int scratch_slot) {
+                             unsigned* vout, size_t n, int end_bit, hipStream_t stream, Slot scratch_slot) {
     if (n == 0) return OT_OK;
     if (n <= RS_OWN_MAX) {
         const int64_t seg[2] = {0, (int64_t)n};
@@ -370,7 +370,7 @@ constexpr int SEGSORT_ITEMS = 16;  // items per thread of the segmented sort's t
                                    // measured slower)
 
 ot_status sort_segments_u32_u32(const unsigned* kin, unsigned* kout, const unsigned* vin, unsigned* vout,
-                                const int64_t* seg, int nseg, int end_bit, hipStream_t stream, int scratch_slot,
+                                const int64_t* seg, int nseg, int end_bit, hipStream_t stream, Slot scratch_slot,
                                 const int* dlen) {
     // (10-bit digits, 1024-thread tiles, 3 passes for the 28..30-bit configs[2] keys: measured slower, 624 + 85 us vs
     // 516 + 52 us per 32-frame batch for 4 passes of 8 bits)
@@ -382,7 +382,7 @@ ot_status sort_segments_u32_u32(const unsigned* kin, unsigned* kout, const unsig
 }
 
 ot_status sort_pairs_u32_u32(const unsigned* kin, unsigned* kout, const unsigned* vin, unsigned* vout, size_t n,
-                             int end_bit, hipStream_t stream, int scratch_slot) {
+                             int end_bit, hipStream_t stream, Slot scratch_slot) {
     if (n == 0) return OT_OK;
     if (end_bit < 1) end_bit = 1;
     size_t tmp = 0;
@@ -400,7 +400,8 @@ extern "C" ot_status otx_sort_pairs_u64_u32(const unsigned long long* kin, unsig
                                            unsigned* vout, int64_t n, int32_t end_bit, void* stream) {
     if (n < 0 || (n > 0 && (!kin || !kout || !vin || !vout)) || end_bit < 1 || end_bit > 64)
         return ot::fail(OT_ERR_INVALID_ARGUMENT, "[sort] invalid arguments");
-    ot_status st = ot::sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, end_bit, (hipStream_t)stream, 3);
+    ot_status st =
+        ot::sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, end_bit, (hipStream_t)stream, ot::Slot::SORT_TMP);
     if (st != OT_OK) return st;
     OT_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return OT_OK;
@@ -414,7 +415,8 @@ extern "C" ot_status otx_sort_segments_u32_u32(const unsigned* kin, unsigned* ko
     for (int s = 0; s < nseg; ++s)
         if (seg[s + 1] < seg[s]) return ot::fail(OT_ERR_INVALID_ARGUMENT, "[sort] invalid segments");
     if (seg[nseg] > 0 && (!kin || !kout || !vin || !vout)) return ot::fail(OT_ERR_INVALID_ARGUMENT, "[sort] invalid arguments");
-    ot_status st = ot::sort_segments_u32_u32(kin, kout, vin, vout, seg, nseg, end_bit, (hipStream_t)stream, 3);
+    ot_status st = ot::sort_segments_u32_u32(kin, kout, vin, vout, seg, nseg, end_bit, (hipStream_t)stream,
+                                             ot::Slot::SORT_TMP);
     if (st != OT_OK) return st;
     OT_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return OT_OK;

@@ -186,10 +186,10 @@ ot_status export_list(ot_tsdf* vol, hipStream_t stream, const unsigned** ids, in
     *ids = vol->sorted_ids;
     *n = nu;
     if (vol->dev.shard_world <= 1 || nu == 0) return OT_OK;
-    unsigned* own = (unsigned*)scratch(sizeof(unsigned) * (size_t)nu + 256, 16);
+    unsigned* own = (unsigned*)scratch(sizeof(unsigned) * (size_t)nu + 256, Slot::MESH_NORMALS_WS);
     if (!own) return fail(OT_ERR_HIP, "scratch allocation failed");
     int64_t no = 0;
-    st = compact(nu, OwnedPred{vol->dev, vol->sorted_ids}, OwnedEmit{vol->sorted_ids, own}, stream, &no, 13);
+    st = compact(nu, OwnedPred{vol->dev, vol->sorted_ids}, OwnedEmit{vol->sorted_ids, own}, stream, &no, Slot::OP_COMPACT);
     if (st != OT_OK) return st;
     *ids = own;
     *n = no;
@@ -378,7 +378,7 @@ ot_status tsdf_sorted_units(ot_tsdf* vol, hipStream_t stream, int64_t* n_units) 
             vol->sorted_frame = vol->frame_id;
             return OT_OK;
         }
-        char* ws = (char*)scratch((size_t)nu * 24 + 256, 5);
+        char* ws = (char*)scratch((size_t)nu * 24 + 256, Slot::TSDF_UNIT_SORT);
         if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
         unsigned long long* kin = (unsigned long long*)(ws + 256);
         unsigned long long* kout = kin + nu;
@@ -386,7 +386,7 @@ ot_status tsdf_sorted_units(ot_tsdf* vol, hipStream_t stream, int64_t* n_units) 
         hipLaunchKernelGGL(k_pack_unit_keys, dim3((nu + 255) / 256), dim3(256), 0, stream, vol->dev, nu, pk, kin, vin);
         OT_LAUNCH_CHECK();
         st = sort_pairs_u64_u32(kin, kout, vin, vol->sorted_ids, (size_t)nu, std::min(63, bits[0] + bits[1] + bits[2]),
-                                stream, 3);
+                                stream, Slot::SORT_TMP);
         if (st != OT_OK) return st;
     }
     vol->sorted_units = nu;

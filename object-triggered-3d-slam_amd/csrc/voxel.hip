@@ -15,12 +15,6 @@
 
 namespace ot {
 
-__device__ inline int bits_for(long long v) {  // bits to represent 0..v
-    int b = 1;
-    while (b < 62 && (v >> b) != 0) ++b;
-    return b;
-}
-
 __global__ __launch_bounds__(256) void k_voxel_keys(const double* __restrict__ xyz, int64_t n, double vs,
                                                     Bounds* b, unsigned long long* keys, unsigned* idx) {
     double vmin[3];
@@ -118,15 +112,12 @@ extern "C" ot_status ot_voxel_down_sample(const double* xyz, const double* rgb, 
     if (!xyz || !out_xyz || (rgb && !out_rgb) || (normals && !out_normals))
         return fail(OT_ERR_INVALID_ARGUMENT, "[VoxelDownSample] invalid buffers");
     if (n > 0x7FFFFFFF) return fail(OT_ERR_INVALID_ARGUMENT, "[VoxelDownSample] too many points");
-    char* ws = (char*)scratch(256 + (size_t)n * (8 + 8 + 4 + 4 + 4), 6);
-    if (!ws) return fail(OT_ERR_HIP, "scratch allocation failed");
-    Bounds* b = (Bounds*)ws;
-    unsigned long long* kin = (unsigned long long*)(ws + 256);
-    unsigned long long* kout = kin + n;
-    unsigned* vin = (unsigned*)(kout + n);
-    unsigned* vout = vin + n;
-    int* heads = (int*)(vout + n);
-    unsigned long long* part = (unsigned long long*)scratch(sizeof(unsigned long long) * BOUNDS_BLOCKS * 6, 18);
+    const size_t un = (size_t)n;
+    auto [b, kin, kout, vin, vout, heads] =
+        carve(scratch_of(Slot::VOXEL_WS), Arr<Bounds>{1}, Arr<unsigned long long>{un}, Arr<unsigned long long>{un},
+              Arr<unsigned>{un}, Arr<unsigned>{un}, Arr<int>{un});
+    if (!b) return fail(OT_ERR_HIP, "scratch allocation failed");
+    unsigned long long* part = (unsigned long long*)scratch(sizeof(unsigned long long) * BOUNDS_BLOCKS * 6, Slot::VOXEL_BOUNDS_PARTIALS);
     if (!part) return fail(OT_ERR_HIP, "scratch allocation failed");
     launch_bounds(xyz, n, b, part, stream);
     // key width on the host (same float64 formula as k_voxel_keys) so the radix sort runs only the passes the
@@ -147,10 +138,10 @@ extern "C" ot_status ot_voxel_down_sample(const double* xyz, const double* rgb, 
     hipLaunchKernelGGL(k_voxel_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, xyz, n, voxel_size, b,
                        kin, vin);
     OT_LAUNCH_CHECK();
-    ot_status st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, end_bit, stream, 3);
+    ot_status st = sort_pairs_u64_u32(kin, kout, vin, vout, (size_t)n, end_bit, stream, Slot::SORT_TMP);
     if (st != OT_OK) return st;
     int64_t K = 0;
-    st = compact(n, SegHeadPred{kout}, SegHeadEmit{heads}, stream, &K, 7);  // synchronises
+    st = compact(n, SegHeadPred{kout}, SegHeadEmit{heads}, stream, &K, Slot::VOXEL_HEADS);  // synchronises
     if (st != OT_OK) return st;
     int err = 0;
     OT_HIP_TRY(hipMemcpyAsync(&err, &b->err, sizeof(int), hipMemcpyDeviceToHost, stream));
