@@ -547,6 +547,49 @@ ot_status ot_mesh_remove_triangles_by_mask(const int32_t* triangles, int64_t n_t
 ot_status ot_mesh_remove_unreferenced_vertices(int64_t n_vertices, int32_t* triangles_inout, int64_t n_triangles,
                                                int32_t* out_kept_old_index, int64_t* n_kept_host, void* stream);
 
+/* Adjacency, smoothing / sharpening filters and vertex clustering ("mesh filters").  Device pointers
+ * unless the name ends in _host; arguments are checked before any device work, and an entry that takes triangles
+ * refuses an index outside [0, n_vertices) before anything else runs ("[<Call>] triangle index out of range
+ * [0, n_vertices)").
+ *
+ * mesh.compute_adjacency_list() as a CSR: for every triangle (a, b, c), b and c are neighbours of a, a and c of b, a
+ * and b of c; repeats collapse, and (a, a, b) makes a its own neighbour.  out_offsets int32 [n_vertices + 1];
+ * out_neighbours int32 [capacity 6 n_triangles], row v = [offsets[v], offsets[v + 1]) in ascending neighbour index;
+ * *n_entries_host = offsets[n_vertices].  6 n_triangles must fit 31 bits.  Synchronises. */
+ot_status ot_mesh_compute_adjacency(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                                    int32_t* out_offsets, int32_t* out_neighbours, int64_t* n_entries_host,
+                                    void* stream);
+/* mesh.filter_smooth_simple / _laplacian / _taubin / filter_sharpen over that CSR (n_entries = offsets[n_vertices]; a
+ * CSR that does not fit n_vertices is refused).  kind: 0 simple, 1 Laplacian (p0 = lambda), 2 Taubin (p0 = lambda,
+ * p1 = mu: each iteration a Laplacian step with lambda, then one with mu), 3 sharpen (p0 = strength).  scope: bit 0
+ * vertices, bit 1 normals, bit 2 colours.  An attribute is filtered when its scope bit is set and its input is not
+ * NULL, and copied to its output otherwise; iterations <= 0 copies everything.  N(v) in ascending index, n = |N(v)|,
+ * every sum one left-to-right float64 chain, every step reading the previous step's values only:
+ *   simple     s = x[v]; s += x[w]...; x'[v] = s / (1 + n)
+ *   Laplacian  wt = 1 / (|p[v] - p[w]| + 1e-12) from the previous positions; W += wt, S += wt x[w] from 0;
+ *              x'[v] = x[v] + lambda (S / W - x[v])
+ *   sharpen    s += x[w] from 0; x'[v] = x[v] (1 + strength n) - strength s
+ * A vertex without neighbours keeps its attributes.  Outputs must not alias inputs; an output is required for every
+ * input given.  Ordered on `stream`. */
+ot_status ot_mesh_filter(int32_t kind, const double* vertices, const double* normals /* nullable */,
+                         const double* colors /* nullable */, int64_t n_vertices, const int32_t* offsets,
+                         const int32_t* neighbours, int64_t n_entries, int32_t iterations, double p0, double p1,
+                         int32_t scope, double* out_vertices, double* out_normals, double* out_colors, void* stream);
+/* mesh.simplify_vertex_clustering(voxel_size, contraction): contraction 0 = Average (1 = Quadric is refused).  Voxel
+ * key floor((p - (min_bound - voxel_size / 2)) / voxel_size) per axis in float64, with ot_voxel_down_sample's
+ * refusals ("voxel_size <= 0.", "voxel_size is too small.").  New vertex k is the k-th voxel by first appearance in
+ * ascending old vertex index; its position, normal and colour are the sums over its old vertices in ascending index,
+ * from 0, divided by their number (normals not normalised).  A triangle whose mapped corners are not all different is
+ * dropped; the others are rotated to start at their smallest index, and one per distinct triple is kept (a flip is
+ * another triple), in ascending index of the first source triangle.  out_vertices / out_normals / out_colors have room
+ * for n_vertices rows, out_triangles for n_triangles.  Synchronises. */
+ot_status ot_mesh_simplify_vertex_clustering(const double* vertices, const double* normals /* nullable */,
+                                             const double* colors /* nullable */, int64_t n_vertices,
+                                             const int32_t* triangles, int64_t n_triangles, double voxel_size,
+                                             int32_t contraction, double* out_vertices, double* out_normals,
+                                             double* out_colors, int64_t* n_out_vertices_host, int32_t* out_triangles,
+                                             int64_t* n_out_triangles_host, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Hybrid map — fusion/hybrid_map.py
  * ------------------------------------------------------------------------------------------------- */

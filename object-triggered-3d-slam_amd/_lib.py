@@ -124,6 +124,9 @@ SIGNATURES = {
     "ot_mesh_flag_duplicated_triangles": [_p, _i64, _i64, _p, _p],
     "ot_mesh_remove_triangles_by_mask": [_p, _i64, _p, _p, _pi64, _p],
     "ot_mesh_remove_unreferenced_vertices": [_i64, _p, _i64, _p, _pi64, _p],
+    "ot_mesh_compute_adjacency": [_p, _i64, _i64, _p, _p, _pi64, _p],
+    "ot_mesh_filter": [_i32, _p, _p, _p, _i64, _p, _p, _i64, _i32, _d, _d, _i32, _p, _p, _p, _p],
+    "ot_mesh_simplify_vertex_clustering": [_p, _p, _p, _i64, _p, _i64, _d, _i32, _p, _p, _p, _pi64, _p, _pi64, _p],
     "ot_occupancy_to_points": [_p, _i32, _i32, _i32, _d, _d, _d, _p, _pi64, _p],
     "ot_grid_smart_paste": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _pi64, _p],
     "ot_voxel_key_diff": [_p, _i64, _p, _i64, _d, _p, _p, _pi64, _p, _pi64, _p],

@@ -29,13 +29,14 @@
 
 #include "compact.h"
 #include "mesh_area.h"
+#include "mesh_components.h"
 #include "sort.h"
 #include "union_find.h"
 
 namespace ot {
 
 
-static int index_bits(int64_t nv) {  // bit width of the largest valid index, nv <= 2^31 - 1
+int index_bits(int64_t nv) {  // bit width of the largest valid index, nv <= 2^31 - 1
     int b = 1;
     while (b < 31 && ((nv - 1) >> b) != 0) ++b;
     return b;
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(256) void k_mcc_renumber(int32_t* __restrict__ T, i
 static inline dim3 blocks_of(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // sizes every entry refuses before any device work
-static ot_status check_sizes(const char* who, int64_t nt, int64_t nv) {
+ot_status check_sizes(const char* who, int64_t nt, int64_t nv) {
     if (nt < 0 || nv < 0) return fail(OT_ERR_INVALID_ARGUMENT, std::string("[") + who + "] negative size");
     if (nt > 0x7FFFFFFF / 3 || nv > 0x7FFFFFFF)
         return fail(OT_ERR_INVALID_ARGUMENT, std::string("[") + who + "] mesh too large (3 n_triangles and n_vertices "
@@ -251,7 +252,7 @@ static ot_status check_sizes(const char* who, int64_t nt, int64_t nv) {
 }
 
 // the range check over the triangle array alone (synchronises)
-static ot_status check_indices(const char* who, const int32_t* T, int64_t nt, int64_t nv, hipStream_t stream) {
+ot_status check_indices(const char* who, const int32_t* T, int64_t nt, int64_t nv, hipStream_t stream) {
     if (nt == 0) return OT_OK;
     int* bad = (int*)scratch(64, Slot::MCC_BAD);
     if (!bad) return fail(OT_ERR_HIP, "scratch allocation failed");
@@ -262,6 +263,29 @@ static ot_status check_indices(const char* who, const int32_t* T, int64_t nt, in
     OT_HIP_TRY(hipMemcpyAsync(&h, bad, sizeof(int), hipMemcpyDeviceToHost, stream));
     OT_HIP_TRY(hipStreamSynchronize(stream));
     if (h) return fail(OT_ERR_INVALID_ARGUMENT, std::string("[") + who + "] triangle index out of range [0, n_vertices)");
+    return OT_OK;
+}
+
+// the duplicate mask of range-checked triangles (mesh_components.h); queued on the stream, no synchronisation
+ot_status flag_duplicated_triangles(const int32_t* triangles, int64_t nt, int64_t n_vertices,
+                                    unsigned char* out_remove_mask, hipStream_t stream) {
+    const size_t unt = (size_t)nt;
+    auto [ka, kb, va, vb] = carve(scratch_of(Slot::MCC_WS), Arr<unsigned long long>{unt}, Arr<unsigned long long>{unt},
+                                  Arr<unsigned>{unt}, Arr<unsigned>{unt});
+    if (!ka) return fail(OT_ERR_HIP, "scratch allocation failed");
+    const int bits = index_bits(n_vertices);
+    hipLaunchKernelGGL(k_mcc_dup_k2, blocks_of(nt), dim3(256), 0, stream, triangles, nt, ka, va);
+    OT_LAUNCH_CHECK();
+    ot_status st = sort_pairs_u64_u32(ka, kb, va, vb, (size_t)nt, bits, stream, Slot::SORT_TMP);  // by the third component
+    if (st != OT_OK) return st;
+    hipLaunchKernelGGL(k_mcc_dup_k01, blocks_of(nt), dim3(256), 0, stream, triangles, nt, bits, (const unsigned*)vb,
+                       ka);
+    OT_LAUNCH_CHECK();
+    st = sort_pairs_u64_u32(ka, kb, vb, va, (size_t)nt, 2 * bits, stream, Slot::SORT_TMP);  // then by the first two
+    if (st != OT_OK) return st;
+    hipLaunchKernelGGL(k_mcc_dup_flag, blocks_of(nt), dim3(256), 0, stream, triangles, nt, (const unsigned*)va,
+                       out_remove_mask);
+    OT_LAUNCH_CHECK();
     return OT_OK;
 }
 
@@ -354,23 +378,8 @@ ot_status ot_mesh_flag_duplicated_triangles(const int32_t* triangles, int64_t n_
     if (nt == 0) return OT_OK;
     st = check_indices(who, triangles, nt, n_vertices, stream);
     if (st != OT_OK) return st;
-    const size_t unt = (size_t)nt;
-    auto [ka, kb, va, vb] = carve(scratch_of(Slot::MCC_WS), Arr<unsigned long long>{unt}, Arr<unsigned long long>{unt},
-                                  Arr<unsigned>{unt}, Arr<unsigned>{unt});
-    if (!ka) return fail(OT_ERR_HIP, "scratch allocation failed");
-    const int bits = index_bits(n_vertices);
-    hipLaunchKernelGGL(k_mcc_dup_k2, blocks_of(nt), dim3(256), 0, stream, triangles, nt, ka, va);
-    OT_LAUNCH_CHECK();
-    st = sort_pairs_u64_u32(ka, kb, va, vb, (size_t)nt, bits, stream, Slot::SORT_TMP);  // by the third component
+    st = flag_duplicated_triangles(triangles, nt, n_vertices, out_remove_mask, stream);
     if (st != OT_OK) return st;
-    hipLaunchKernelGGL(k_mcc_dup_k01, blocks_of(nt), dim3(256), 0, stream, triangles, nt, bits, (const unsigned*)vb,
-                       ka);
-    OT_LAUNCH_CHECK();
-    st = sort_pairs_u64_u32(ka, kb, vb, va, (size_t)nt, 2 * bits, stream, Slot::SORT_TMP);  // then by the first two
-    if (st != OT_OK) return st;
-    hipLaunchKernelGGL(k_mcc_dup_flag, blocks_of(nt), dim3(256), 0, stream, triangles, nt, (const unsigned*)va,
-                       out_remove_mask);
-    OT_LAUNCH_CHECK();
     OT_HIP_TRY(hipStreamSynchronize(stream));
     return OT_OK;
 }

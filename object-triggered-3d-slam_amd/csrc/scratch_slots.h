@@ -83,11 +83,16 @@ enum class Slot : int {
     // mesh_components.hip
     MCC_WS,
     MCC_COMPACT,
-    MCC_BAD,
+    MCC_BAD,  // the refusal word of check_indices; shared with mesh_filter.hip's CSR check (each reads it back at once)
     // segment_plane.hip
     SP_CANDIDATES,
     SP_TIES,
     SP_FINAL,
+    // mesh_filter.hip
+    MF_WS,               // adjacency: keys / values of the sort; clustering: bounds, sort, heads, rows, mapped triangles
+    MF_COMPACT,          // block counts of its compactions (consumed inside compact())
+    MF_BOUNDS_PARTIALS,  // clustering: bounds partials
+    MF_PING,             // filters: the second buffer of the ping-pong
     COUNT
 };
 

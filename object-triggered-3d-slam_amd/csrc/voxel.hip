@@ -8,96 +8,9 @@
 //   5. reduce      : one lane per voxel sums its points in index order and divides by the count — the same
 //                    float64 operation sequence as Open3D's AccumulatedPoint, so averages are bit-exact.
 // Output voxels are in key order (Open3D: unordered_map order; parity compares sorted sets).
-#include <cmath>
+#include "voxel_keys.h"
 
-#include "compact.h"
 #include "sort.h"
-
-namespace ot {
-
-__global__ __launch_bounds__(256) void k_voxel_keys(const double* __restrict__ xyz, int64_t n, double vs,
-                                                    Bounds* b, unsigned long long* keys, unsigned* idx) {
-    double vmin[3];
-    int bits[3];
-    long long kmax[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        vmin[a] = ordered_to_dbl(b->mn[a]) - vs * 0.5;
-        const double vmax = ordered_to_dbl(b->mx[a]) + vs * 0.5;
-        kmax[a] = (long long)floor((vmax - vmin[a]) / vs);
-        bits[a] = bits_for(kmax[a]);
-    }
-    const double ext = fmax(fmax(ordered_to_dbl(b->mx[0]) + vs * 0.5 - vmin[0], ordered_to_dbl(b->mx[1]) + vs * 0.5 - vmin[1]),
-                            ordered_to_dbl(b->mx[2]) + vs * 0.5 - vmin[2]);
-    const bool too_small = vs * 2147483647.0 < ext;
-    const bool too_wide = bits[0] + bits[1] + bits[2] > 64;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i == 0 && (too_small || too_wide)) b->err = too_small ? 1 : 2;
-    if (i >= n) return;
-    long long k[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) k[a] = (long long)(int)floor((xyz[i * 3 + a] - vmin[a]) / vs);
-    keys[i] = ((unsigned long long)k[0] << (bits[1] + bits[2])) | ((unsigned long long)k[1] << bits[2]) |
-              (unsigned long long)k[2];
-    idx[i] = (unsigned)i;
-}
-
-__global__ __launch_bounds__(256) void k_voxel_reduce(const double* __restrict__ xyz, const double* __restrict__ rgb,
-                                                      const double* __restrict__ nrm, const unsigned* __restrict__ sidx,
-                                                      const unsigned long long* __restrict__ skeys,
-                                                      const int* __restrict__ heads, int64_t K, int64_t n,
-                                                      const Bounds* b, double vs, double* oxyz, double* orgb,
-                                                      double* onrm, int32_t* okeys) {
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= K) return;
-    const int64_t beg = heads[s];
-    const int64_t end = (s + 1 < K) ? heads[s + 1] : n;
-    double p[3] = {0, 0, 0}, c[3] = {0, 0, 0}, q[3] = {0, 0, 0};
-    // points in batches of 4: the batch's index and row loads are all issued before its (in-order) sums
-    constexpr int VB = 4;
-    for (int64_t j0 = beg; j0 < end; j0 += VB) {
-        int64_t ii[VB];
-#pragma unroll
-        for (int k = 0; k < VB; ++k) ii[k] = sidx[j0 + k < end ? j0 + k : j0];
-        double xp[VB][3], xc[VB][3], xq[VB][3];
-#pragma unroll
-        for (int k = 0; k < VB; ++k)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                xp[k][a] = xyz[ii[k] * 3 + a];
-                xc[k][a] = rgb ? rgb[ii[k] * 3 + a] : 0.0;
-                xq[k][a] = nrm ? nrm[ii[k] * 3 + a] : 0.0;
-            }
-#pragma unroll
-        for (int k = 0; k < VB; ++k) {
-            if (j0 + k >= end) break;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                p[a] += xp[k][a];
-                if (rgb) c[a] += xc[k][a];
-                if (nrm) q[a] += xq[k][a];
-            }
-        }
-    }
-    const double cnt = (double)(end - beg);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        oxyz[s * 3 + a] = p[a] / cnt;
-        if (rgb) orgb[s * 3 + a] = c[a] / cnt;
-        if (nrm) onrm[s * 3 + a] = q[a] / cnt;
-    }
-    if (okeys) {
-        // recover the integer key of this voxel from its first point (same formula as k_voxel_keys)
-        const int64_t i = sidx[beg];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double vmin = ordered_to_dbl(b->mn[a]) - vs * 0.5;
-            okeys[s * 3 + a] = (int)floor((xyz[i * 3 + a] - vmin) / vs);
-        }
-    }
-}
-
-}  // namespace ot
 
 using namespace ot;
 
@@ -125,16 +38,7 @@ extern "C" ot_status ot_voxel_down_sample(const double* xyz, const double* rgb, 
     Bounds hb;
     OT_HIP_TRY(hipMemcpyAsync(&hb, b, sizeof(Bounds), hipMemcpyDeviceToHost, stream));
     OT_HIP_TRY(hipStreamSynchronize(stream));
-    int end_bit = 0;
-    for (int a = 0; a < 3; ++a) {
-        const double vmin = ordered_to_dbl(hb.mn[a]) - voxel_size * 0.5;
-        const double vmax = ordered_to_dbl(hb.mx[a]) + voxel_size * 0.5;
-        const double span = std::floor((vmax - vmin) / voxel_size);
-        int bits = 1;
-        while (bits < 62 && span >= std::ldexp(1.0, bits)) ++bits;
-        end_bit += bits;
-    }
-    end_bit = std::min(end_bit, 64);
+    const int end_bit = voxel_key_end_bit(hb, voxel_size);
     hipLaunchKernelGGL(k_voxel_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, xyz, n, voxel_size, b,
                        kin, vin);
     OT_LAUNCH_CHECK();
@@ -149,7 +53,8 @@ extern "C" ot_status ot_voxel_down_sample(const double* xyz, const double* rgb, 
     if (err == 1) return fail(OT_ERR_INVALID_ARGUMENT, "[VoxelDownSample] voxel_size is too small.");
     if (err == 2) return fail(OT_ERR_INVALID_ARGUMENT, "[VoxelDownSample] voxel grid exceeds 64-bit key packing");
     hipLaunchKernelGGL(k_voxel_reduce, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, xyz, rgb, normals,
-                       vout, kout, heads, K, n, b, voxel_size, out_xyz, out_rgb, out_normals, out_keys);
+                       vout, kout, heads, K, n, b, voxel_size, out_xyz, out_rgb, out_normals, out_keys,
+                       (const int*)nullptr);
     OT_LAUNCH_CHECK();
     OT_HIP_TRY(hipStreamSynchronize(stream));
     *n_out_host = K;

@@ -8,6 +8,7 @@ Every compute method calls the C ABI; none has a CPU implementation.
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import importlib
 import math
 
@@ -784,6 +785,24 @@ def _unproject(depth_img, color_img, intrinsic, extrinsic, stride):
 
 
 # -------------------------------------------------------------------------------------- TriangleMesh
+class FilterScope(enum.IntEnum):
+    """open3d.geometry.FilterScope: which attributes a mesh filter changes (the others are copied through)."""
+    All = 0
+    Color = 1
+    Normal = 2
+    Vertex = 3
+
+
+class SimplificationContraction(enum.IntEnum):
+    """open3d.geometry.SimplificationContraction (Quadric is not supported by this build)."""
+    Average = 0
+    Quadric = 1
+
+
+_SCOPE_BITS = {FilterScope.All: 7, FilterScope.Vertex: 1, FilterScope.Normal: 2, FilterScope.Color: 4}
+_FILTER_SIMPLE, _FILTER_LAPLACIAN, _FILTER_TAUBIN, _FILTER_SHARPEN = 0, 1, 2, 3
+
+
 class TriangleMesh:
     """open3d.geometry.TriangleMesh: vertices f64 (V,3), triangles i32 (T,3), vertex colors / normals."""
 
@@ -793,8 +812,9 @@ class TriangleMesh:
             host=np.zeros((0, 3), np.int32))
         self._vc = None
         self._vn = None
-
         self._mc = None  # (volume handle, extraction serial) of a mesh fresh out of extract_triangle_mesh
+        self._adj = None  # (offsets i32 [V + 1], neighbours i32 [E]) on the device: compute_adjacency_list
+
     @property
     def vertices(self):
         self._settle()
@@ -804,6 +824,7 @@ class TriangleMesh:
     def vertices(self, v):
         self._v = _Arr.wrap(v, np.float64, 3)
         self._mc = None
+        self._adj = None
 
     @property
     def triangles(self):
@@ -814,6 +835,7 @@ class TriangleMesh:
     def triangles(self, t):
         self._t = _Arr.wrap(t, np.int32, 3)
         self._mc = None
+        self._adj = None
 
     @property
     def vertex_colors(self):
@@ -947,6 +969,7 @@ class TriangleMesh:
                C.byref(k), D.stream_ptr())
         self._t = _Arr(dev=out[:k.value])
         self._mc = None
+        self._adj = None
         return self
 
     def remove_triangles_by_mask(self, triangle_mask):
@@ -958,6 +981,7 @@ class TriangleMesh:
         self._settle()
         if len(mask) == 0:
             self._mc = None
+            self._adj = None
             return self
         return self._replace_triangles(D.to_device(mask.astype(np.uint8)))
 
@@ -975,6 +999,7 @@ class TriangleMesh:
         nt = len(self._t)
         if nt == 0:
             self._mc = None
+            self._adj = None
             return self
         mask = D.empty((nt,), "uint8")
         L.call(entry, D.ptr(self._t.dev()), nt, len(self._v), D.ptr(mask), D.stream_ptr())
@@ -997,6 +1022,7 @@ class TriangleMesh:
         self._settle()
         nv, nt = len(self._v), len(self._t)
         self._mc = None
+        self._adj = None
         if nv == 0:
             return self
         tri = self._t.dev().clone() if nt else None  # rewritten in place: the mesh's own copy stays whole on an error
@@ -1019,6 +1045,127 @@ class TriangleMesh:
         if nt:
             self._t = _Arr(dev=tri)
         return self
+
+    # --- adjacency, smoothing / sharpening filters, vertex clustering (DESIGN.md §4 "mesh filters") ---
+    def compute_adjacency_list(self):
+        """TriangleMesh::ComputeAdjacencyList — ot_mesh_compute_adjacency: for every triangle each corner gets the
+        other two as neighbours (a degenerate (a, a, b) makes a its own neighbour).  Kept on the device as a CSR with
+        every row in ascending order.  Assigning `triangles` or `vertices` and every clean-up call drop it; edits made
+        in place through a view of `triangles` do not, as in Open3D: call this again after them."""
+        self._settle()
+        nv, nt = len(self._v), len(self._t)
+        if nv == 0 and nt == 0:
+            self._adj = None
+            return self
+        offsets = D.empty((nv + 1,), "int32")
+        nbr = D.empty((6 * nt,), "int32") if nt else None
+        k = C.c_int64(0)
+        L.call("ot_mesh_compute_adjacency", D.ptr(self._t.dev()) if nt else None, nt, nv, D.ptr(offsets), D.ptr(nbr),
+               C.byref(k), D.stream_ptr())
+        self._adj = (offsets, nbr[:k.value].clone() if nt else D.empty((0,), "int32"))
+        return self
+
+    def has_adjacency_list(self):
+        return len(self._v) > 0 and self._adj is not None and len(self._adj[0]) == len(self._v) + 1
+
+    @property
+    def adjacency_list(self):
+        """A list of Python sets of ints, one per vertex (empty before compute_adjacency_list)."""
+        if not self.has_adjacency_list():
+            return []
+        off = D.to_host(self._adj[0]).tolist()
+        nbr = D.to_host(self._adj[1]).tolist()
+        return [set(nbr[off[v]:off[v + 1]]) for v in range(len(off) - 1)]
+
+    def _copy_mesh(self):
+        """A new mesh with copies of the vertices, triangles, normals and colours (and the same adjacency list)."""
+        self._settle()
+        out = TriangleMesh()
+        out._v, out._t = self._v.copy(), self._t.copy()
+        out._vc = self._vc.copy() if self._vc is not None else None
+        out._vn = self._vn.copy() if self._vn is not None else None
+        out._adj = self._adj if self.has_adjacency_list() else None  # never written after it is built
+        return out
+
+    def _filter(self, kind, iterations, p0, p1, scope):
+        scope = FilterScope(scope)
+        out = self._copy_mesh()
+        nv = len(self._v)
+        iterations = int(iterations)
+        if nv == 0 or iterations <= 0:
+            return out
+        if not out.has_adjacency_list():
+            out.compute_adjacency_list()
+        offsets, nbr = out._adj
+        vn = self._vn if self.has_vertex_normals() and len(self._vn) == nv else None
+        vc = self._vc if self.has_vertex_colors() and len(self._vc) == nv else None
+        oV = D.empty((nv, 3), "float64")
+        oN = D.empty((nv, 3), "float64") if vn is not None else None
+        oC = D.empty((nv, 3), "float64") if vc is not None else None
+        L.call("ot_mesh_filter", kind, D.ptr(self._v.dev()), D.ptr(vn.dev()) if vn is not None else None,
+               D.ptr(vc.dev()) if vc is not None else None, nv, D.ptr(offsets), D.ptr(nbr) if len(nbr) else None,
+               len(nbr), iterations, float(p0), float(p1), _SCOPE_BITS[scope], D.ptr(oV), D.ptr(oN), D.ptr(oC),
+               D.stream_ptr())
+        out._v = _Arr(dev=oV)
+        if oN is not None:
+            out._vn = _Arr(dev=oN)
+        if oC is not None:
+            out._vc = _Arr(dev=oC)
+        return out
+
+    def filter_smooth_simple(self, number_of_iterations=1, scope=FilterScope.All):
+        """TriangleMesh::FilterSmoothSimple: x'[v] = (x[v] + the sum of x[w] over v's neighbours in ascending index)
+        / (1 + n), every iteration from the previous one's values.  Returns a new mesh."""
+        return self._filter(_FILTER_SIMPLE, number_of_iterations, 0.0, 0.0, scope)
+
+    def filter_smooth_laplacian(self, number_of_iterations=1, lambda_filter=0.5, scope=FilterScope.All):
+        """TriangleMesh::FilterSmoothLaplacian: x'[v] = x[v] + lambda (S / W - x[v]) with the inverse-distance
+        weights 1 / (|p[v] - p[w]| + 1e-12) of the previous positions.  Returns a new mesh."""
+        return self._filter(_FILTER_LAPLACIAN, number_of_iterations, lambda_filter, 0.0, scope)
+
+    def filter_smooth_taubin(self, number_of_iterations=1, lambda_filter=0.5, mu=-0.53, scope=FilterScope.All):
+        """TriangleMesh::FilterSmoothTaubin: each iteration is a Laplacian step with lambda, then one with mu, the
+        second on the first one's output.  Returns a new mesh."""
+        return self._filter(_FILTER_TAUBIN, number_of_iterations, lambda_filter, mu, scope)
+
+    def filter_sharpen(self, number_of_iterations=1, strength=1.0, scope=FilterScope.All):
+        """TriangleMesh::FilterSharpen: x'[v] = x[v] (1 + strength n) - strength (the sum of x[w]).  Returns a new
+        mesh."""
+        return self._filter(_FILTER_SHARPEN, number_of_iterations, strength, 0.0, scope)
+
+    def simplify_vertex_clustering(self, voxel_size, contraction=SimplificationContraction.Average):
+        """TriangleMesh::SimplifyVertexClustering with Average contraction — ot_mesh_simplify_vertex_clustering.  The
+        vertices of one voxel become one vertex (averages of position, normal and colour in ascending old index),
+        numbered by first appearance; triangles that collapse are dropped, and one of each rotation survives, in the
+        order of their first source triangle.  Returns a new mesh."""
+        contraction = SimplificationContraction(contraction)
+        if contraction == SimplificationContraction.Quadric:
+            raise RuntimeError("[SimplifyVertexClustering] SimplificationContraction.Quadric is not supported by this "
+                               "build (Average only)")
+        if not voxel_size > 0.0:
+            raise RuntimeError("[SimplifyVertexClustering] voxel_size <= 0.")
+        self._settle()
+        nv, nt = len(self._v), len(self._t)
+        out = TriangleMesh()
+        if nv == 0 and nt == 0:
+            return out
+        vn = self._vn if self.has_vertex_normals() and len(self._vn) == nv else None
+        vc = self._vc if self.has_vertex_colors() and len(self._vc) == nv else None
+        oV = D.empty((nv, 3), "float64")
+        oN = D.empty((nv, 3), "float64") if vn is not None else None
+        oC = D.empty((nv, 3), "float64") if vc is not None else None
+        oT = D.empty((nt, 3), "int32") if nt else None
+        kv, kt = C.c_int64(0), C.c_int64(0)
+        L.call("ot_mesh_simplify_vertex_clustering", D.ptr(self._v.dev()) if nv else None,
+               D.ptr(vn.dev()) if vn is not None else None, D.ptr(vc.dev()) if vc is not None else None, nv,
+               D.ptr(self._t.dev()) if nt else None, nt, float(voxel_size), int(contraction), D.ptr(oV), D.ptr(oN),
+               D.ptr(oC), C.byref(kv), D.ptr(oT), C.byref(kt), D.stream_ptr())
+        out._v = _Arr(dev=oV[:kv.value].clone())
+        out._vn = _Arr(dev=oN[:kv.value].clone()) if oN is not None else None
+        out._vc = _Arr(dev=oC[:kv.value].clone()) if oC is not None else None
+        if nt:
+            out._t = _Arr(dev=oT[:kt.value].clone())
+        return out
 
     def sample_points_uniformly(self, number_of_points=100, use_triangle_normal=False, seed=0):
         """TriangleMesh::SamplePointsUniformly (reconstruct_rgbd_filter.py:123) with a seeded counter RNG."""
