@@ -268,7 +268,9 @@ ot_status ot_tsdf_integrate_u16(ot_tsdf* vol, const uint16_t* depth, const uint8
                                 double depth_scale, double depth_trunc, void* stream);
 /* n frames of a scan already resident in device memory in one call: frame k's u16 depth at depth + k*W*H, its RGB8 at
  * color + 3*k*W*H (color may be NULL), its extrinsic at extrinsics + 16*k (host).  The same queueing, batching and
- * bits as n calls of ot_tsdf_integrate_u16, without n host round trips (the front of one object's latency). */
+ * bits as n calls of ot_tsdf_integrate_u16, without n host round trips (the front of one object's latency); and when
+ * the call leaves 64 frames or more queued (or the batch size, if smaller) their batch is started before it returns,
+ * so a scan of 64..127 frames does not wait for the next reader under the default batch size of 128. */
 ot_status ot_tsdf_integrate_u16_frames(ot_tsdf* vol, int32_t n, const uint16_t* depth, const uint8_t* color,
                                        const ot_intrinsics* in, const double* extrinsics, double depth_scale,
                                        double depth_trunc, void* stream);
@@ -276,7 +278,11 @@ ot_status ot_tsdf_flush(ot_tsdf* vol, void* stream);
 /* Frames queued on the host for the next batch (their input buffers are still referenced; every frame queued before
  * them has been enqueued on its stream).  Host-only, no synchronisation. */
 ot_status ot_tsdf_pending_frames(const ot_tsdf* vol, int32_t* n_host);
-/* Batch size used by ot_tsdf_integrate_u16 (1 = integrate immediately, default and maximum 64). */
+/* Batch size used by ot_tsdf_integrate_u16 (1 = integrate immediately).  Default and maximum 128 for a whole volume
+ * whose batches run on the caller's stream; a sharded volume and the double-buffered, split and deferred front ends
+ * batch by at most 64 whatever is set here.  A caller's frame must stay valid until its batch has run (the batch fills,
+ * a flush or a reader): with the default that is up to 128 calls.  The first batch of more than 64 frames reallocates
+ * the volume's staging to the batch size once (128 frames of 640 x 480: 315 MB, one stream synchronise). */
 ot_status ot_tsdf_set_batch(ot_tsdf* vol, int32_t max_frames);
 /* Double-buffered batch front end (spatial sharding of one object: reconstruct_rgbd_filter.py:88-109):
  * with mode 1 batch k+1's staging, touch and unit headers run on the caller's stream while batch k's integrate runs on

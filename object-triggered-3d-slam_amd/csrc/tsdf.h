@@ -3,7 +3,7 @@
 // HBM layout (one allocation per field group, sized at create time):
 //   hash table  : open addressing, linear probing, capacity = pow2 >= 4 * max_units
 //                 hkeys u64 (packed int3 unit key, KEY_EMPTY = ~0), hvals i32 (unit id, -1 = not allocated),
-//                 fmask u64 (frames of the current batch touching the unit)
+//                 fmask 3 x u64 (frames of the current batch touching the unit, two words, and a claim word)
 //   unit pool   : max_units blocks of 16^3 voxels, field-planar inside a block:
 //                 vox[id][field][z][x*16 + y], field = {tsdf, weight, r, g, b} (f32).  One 256-lane
 //                 workgroup owns a block; lane (x, y) walks z, so every z step is one coalesced 1-KiB row
@@ -58,7 +58,9 @@ struct TsdfDev {
     float* vox;                 // unit pool: max_units records of unit_floats floats
     int unit_floats;            // record stride: UNIT_FLOATS (float32 colour / NoColor) or UNIT_FLOATS_C64
     int color64;                // 1: the record's colour planes are float64 (colour precision 64, RGB8 volumes)
-    unsigned long long* fmask;  // per hash slot: frames of the current batch that touch the unit (bit f)
+    // per hash slot, FMASK_STRIDE words: the frames of the current batch that touch the unit (frame f is bit f & 63 of
+    // word f >> 6, at fmask[slot * FMASK_STRIDE + (f >> 6)]), then the slot's claim word (FMASK_CLAIM)
+    unsigned long long* fmask;
     int* bslots;                // hash slots touched by the current batch (first-touch order)
     void* work;                 // per touched slot of the batch: unit header (UnitWork, 32 B) for the integrate
     int hash_mask;
@@ -69,6 +71,17 @@ struct TsdfDev {
     int shard_mode;   // SHARD_BLOCKS: hashed blocks of 2^shift units; SHARD_SECTORS: azimuth sectors around a centre
     int shard_cx2, shard_cy2;  // sector centre in half units (round(2 * centre / unit_length)) per axis
 };
+// Frame masks: two 64-bit words per slot, so a batch has up to 128 frames.  A touch workgroup's frames lie in one word
+// and it merges its bits with one atomicOr on that word.  In a batch of more than 64 frames the first bits of the two
+// words may be set by different workgroups at the same time, so "the old word was 0" no longer says "first touch of the
+// batch": the workgroup that sets a word's first bits then also draws the slot's claim (atomicExch on the slot's third
+// word), and the one that finds it free lists the slot in bslots -- once per batch, whichever word came first.
+// k_batch_units clears all three words.
+constexpr int FMASK_WORDS = 2;
+constexpr int FMASK_CLAIM = FMASK_WORDS;       // index of the claim word in a slot's words
+constexpr int FMASK_STRIDE = FMASK_WORDS + 1;  // u64 words per slot
+constexpr int WORD_FRAMES = 64;  // frames per mask word: the batch cap of everything that reads one word only
+inline size_t fmask_bytes(int64_t cap) { return sizeof(unsigned long long) * FMASK_STRIDE * (size_t)cap; }
 constexpr int SHARD_BLOCKS = 0;
 constexpr int SHARD_SECTORS = 1;
 
@@ -173,7 +186,10 @@ __host__ __device__ inline void border_voxel(int b, int& x, int& y, int& z) {
     else y = r - 15, z = 0;
 }
 
-constexpr int MAX_BATCH = 64;      // frames per fused launch (one bit each in fmask)
+// frames per batch: one bit each in a slot's FMASK_WORDS mask words.  A whole volume whose batches run BatchMode::Direct
+// takes up to MAX_BATCH; a sharded volume and the overlap, deferred and split modes read one word and keep WORD_FRAMES
+// (tsdf.hip batch_cap decides, once, for every caller)
+constexpr int MAX_BATCH = FMASK_WORDS * WORD_FRAMES;
 constexpr int OT_MAIL_WORDS = 64;  // capacity of the pinned host mailbox (4-B words per read-back, mail_words)
 // sequence words of the kernels that mail on their own (mail_wait): the marching-cubes scans (words 62, 63: one per
 // scan block) and the units kernel's counters (the last word of the second half)
@@ -248,8 +264,8 @@ struct StageMaskParams {
 struct UnitWork {
     int id;                   // pool id, | 0x80000000 when fresh (state starts at zero), -1 when dropped
     int kx, ky, kz;           // unit key
-    unsigned long long mask;  // frames of the batch that touch the unit (bit f = frame f)
-    unsigned long long pad;
+    unsigned long long mask;   // frames of the batch that touch the unit (bit f = frame f), frames 0..63
+    unsigned long long mask1;  // frames 64..127 (bit f - 64); 0 in a batch of at most 64 frames
 };
 
 // How a batch runs (tsdf.hip plan_batch chooses once per batch; everything after it reads the plan):
@@ -333,7 +349,7 @@ struct ot_tsdf {
     float* mult = nullptr;
     ot_intrinsics mult_intr{};
     bool mult_valid = false;
-    // batching of integrate_u16: frames per fused launch (ot_tsdf_set_batch; 64 = MAX_BATCH, measured best, §4)
+    // batching of integrate_u16: frames per fused launch (ot_tsdf_set_batch; capped by tsdf.hip batch_cap; default: §4.1)
     int batch_max = ot::MAX_BATCH;
     std::vector<ot::PendingFrame> pending;
     ot::BatchFrame* hbframes = nullptr;    // pinned host staging [2][MAX_BATCH]
@@ -368,7 +384,7 @@ struct ot_tsdf {
     int overlap_mode = -1;        // -1 (default) and 0 off, 1 on
     // Split front end of a sharded volume (round 6): the touch stages nothing (only each stride sample's own pixel, for a
     // replay), k_stage_mask marks the image tiles the batch's owned units can project to, k_stage_tiles stages those.
-    unsigned* tmask = nullptr;    // device [MAX_BATCH][tile rows][words per row]
+    unsigned* tmask = nullptr;    // device [WORD_FRAMES][tile rows][words per row] (split batches keep one mask word)
     int64_t tmask_words = 0;
     int tmask_w = 0, tmask_h = 0;  // the image size the masks are laid out for
     int split_mode = -1;          // -1 (default): split for sharded volumes; 0 off; 1 on (test hook)

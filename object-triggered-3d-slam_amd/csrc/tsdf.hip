@@ -9,7 +9,7 @@
 //   (ii)  stride-4 unprojection with camera_pose = inverse(extrinsic) in float64
 //   (iii) touched units = union over samples of [floor((p - trunc)/L), floor((p + trunc)/L)]^3
 //   (iv)  per touched unit, per voxel: project, sample depth, sdf update — all f32, z walked incrementally.
-// Every flush is a batch of 1..64 frames (a single frame is a batch of one): k_batch_touch -> k_batch_units ->
+// Every flush is a batch of 1..128 frames (batch_cap; a single frame is a batch of one): k_batch_touch -> k_batch_units ->
 // k_batch_integrate, below.  The unit pool is unbounded like Open3D's: when a batch needs more units than the pool
 // holds, the pool and the hash grow (records copied, keys rehashed) and the batch's dropped units are integrated
 // again from its staged frames (settle_batch), so the result is the one an unbounded pool gives.
@@ -49,12 +49,13 @@ __device__ inline void st_f64(__amdgpu_buffer_rsrc_t r, int i, double x) {
 }
 
 // ============================================================================ batched (temporal blocking)
-// One launch per batch of F <= 64 frames:
+// One launch per batch of F <= MAX_BATCH frames (128 for a whole volume's direct batches, else 64: batch_cap):
 //   staging           : one 8-B record per pixel of every frame, (float depth, colour r | g << 8 | b << 16), done by
 //                       k_batch_touch's workgroups (each stages a contiguous pixel chunk of its frames)
-//   k_batch_touch     : stride samples of every frame; a unit touched by frame f gets bit f in its slot's
-//                       fmask (64-bit atomicOr); the first bit set in a batch appends the slot to bslots
-//   k_batch_units     : per touched slot: allocate the unit if new, move its frame mask into a 32-B header
+//   k_batch_touch     : stride samples of every frame; a unit touched by frame f gets bit f & 63 in word f >> 6 of its
+//                       slot's fmask (64-bit atomicOr); the batch's first touch of a unit appends the slot to bslots
+//                       (touch_slot: the word's first bits, and in a batch of both words the slot's claim)
+//   k_batch_units     : per touched slot: allocate the unit if new, move its two mask words into a 32-B header
 //   k_batch_integrate : persistent independent waves over (unit, slice) items: a slice's 64 x BZ voxels are
 //                       loaded into registers (5 x BZ VGPRs/lane), the batch's frames are applied in call order
 //                       (ascending bits of the mask) and the state is written back once.  Per-voxel arithmetic is
@@ -153,15 +154,20 @@ __device__ inline void prep_range(const BatchFrame& fr, int64_t q, int64_t q1, i
 
 // The batch's per-frame parameters from the pinned host staging into device memory: one small kernel reading host
 // memory instead of a copy command (the runtime's blit copy cost ~5 us of host API time and left the stream idle ~4 us
-// behind it, on every batch's critical path: one object's timeline, r05m).  One 16-B word per lane, so every PCIe read
-// is in flight at once (a 256-lane loop took 8.4 us: four round trips, r05n)
+// behind it, on every batch's critical path: one object's timeline, r05m).  Up to two 16-B words per lane (the second
+// only past 78 frames), both loaded before either is stored, so every PCIe read is in flight at once (a 256-lane loop
+// took 8.4 us: four round trips, r05n)
 static_assert(sizeof(BatchFrame) % 16 == 0, "BatchFrame is copied in 16-B words");
 constexpr int COPY_FRAMES_LANES = 1024;
-static_assert(sizeof(BatchFrame) / 16 * MAX_BATCH <= COPY_FRAMES_LANES, "one word per lane");
+static_assert(sizeof(BatchFrame) / 16 * MAX_BATCH <= 2 * COPY_FRAMES_LANES, "two words per lane");
 __global__ __launch_bounds__(COPY_FRAMES_LANES) void k_copy_frames(const uint4* __restrict__ src,
                                                                    uint4* __restrict__ dst, int n16) {
-    const int i = threadIdx.x;
-    if (i < n16) dst[i] = src[i];
+    const int i = threadIdx.x, j = i + COPY_FRAMES_LANES;
+    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+    if (i < n16) a = src[i];
+    if (j < n16) b = src[j];
+    if (i < n16) dst[i] = a;
+    if (j < n16) dst[j] = b;
 }
 
 // floor(RN(a / b)) -- Open3D's LocateVolumeUnit on a float64 quotient -- with one multiply in the common case: v =
@@ -175,6 +181,21 @@ __device__ inline int floor_div(double a, double b, double inv_b) {
     return (int)floor(a / b);
 }
 
+// Bits `bits` of the mask word of frame f of `slot`; true: this call lists the slot in bslots (the batch's first touch
+// of the unit).  WIDE: the batch has frames in both words, and the first touch of a word draws the slot's claim
+// (tsdf.h).  !WIDE (a batch of at most WORD_FRAMES frames: every sharded, split, fused and deferred batch): word 0 alone
+// and no claim, the single atomicOr a one-word mask takes.
+template <bool WIDE>
+__device__ inline bool touch_slot(const TsdfDev& d, int slot, int f, unsigned long long bits) {
+    if constexpr (WIDE) {
+        if (atomicOr(&d.fmask[(unsigned)slot * FMASK_STRIDE + (f >> 6)], bits) != 0ull) return false;
+        return atomicExch(&d.fmask[(unsigned)slot * FMASK_STRIDE + FMASK_CLAIM], 1ull) == 0ull;
+    } else {
+        return atomicOr(&d.fmask[(unsigned)slot * FMASK_STRIDE], bits) == 0ull;
+    }
+}
+
+template <bool WIDE>
 __device__ inline void touch_unit_batch(const TsdfDev& d, int f, int slot_cap, int pc, int x, int y, int z) {
     if (!key_in_range(x, y, z)) {
         atomicOr(&d.counters[C_HASHERR], 2);
@@ -187,10 +208,10 @@ __device__ inline void touch_unit_batch(const TsdfDev& d, int f, int slot_cap, i
         atomicOr(&d.counters[C_HASHERR], 1);
         return;
     }
-    const unsigned long long bit = 1ull << f;
-    if (d.fmask[slot] & bit) return;  // fast path; a stale read only costs the atomic below
-    const unsigned long long old = atomicOr(&d.fmask[slot], bit);
-    if (old == 0ull) {
+    const unsigned long long bit = 1ull << (WIDE ? f & 63 : f);
+    // fast path; a stale read only costs the atomic below
+    if (d.fmask[(unsigned)slot * FMASK_STRIDE + (WIDE ? f >> 6 : 0)] & bit) return;
+    if (touch_slot<WIDE>(d, slot, f, bit)) {
         const int pos = atomicAdd(&d.counters[pc], 1);
         if (pos < slot_cap) d.bslots[pos] = slot;
         else atomicOr(&d.counters[C_HASHERR], 1);
@@ -207,6 +228,14 @@ constexpr int TT = 16;          // tile edge in samples
 // workgroup staging a share first, 4 was 1 % faster than 2 (round 3)
 constexpr int TF = 2;
 constexpr int LTAB = 1024;   // LDS table entries (16 B each + a 4-B slot in the list of used entries)
+
+// Frame groups: group g is frames g tf ... g tf + tf - 1.  A group's frames lie in one mask word, so a touch workgroup's
+// LDS masks stay 64-bit and it merges them with one atomicOr: a batch of more than WORD_FRAMES frames takes a group size
+// that divides WORD_FRAMES (touch_group_frames, on the host; TF = 2 does).
+static int touch_group_frames(int tf, int n) {
+    while (n > WORD_FRAMES && WORD_FRAMES % tf) --tf;
+    return tf;
+}
 
 __device__ inline bool lds_merge(unsigned long long* keys, unsigned long long* masks, unsigned short* used, int* nused,
                                  unsigned long long key, unsigned long long bit) {
@@ -387,7 +416,8 @@ struct TouchLds {
 };
 // STAGE: the staging code paths (stage_blocks >= 0) are compiled in; the split front end's touch has none (the touch half
 // of k_integrate_touch: without them it fits 64 VGPRs instead of 96)
-template <bool REPLAY, bool STAGE = !REPLAY>
+// WIDE: the batch may have more than WORD_FRAMES frames (touch_slot); the host launches that form for such a batch only
+template <bool REPLAY, bool STAGE = !REPLAY, bool WIDE = false>
 __device__ __forceinline__ void touch_body(const BatchFrame* __restrict__ frames, const BatchTouchParams& p,
                                            const TsdfDev& d, int nframes, TouchLds& L, int tile, int grp) {
     unsigned long long* s_keys = L.keys;
@@ -414,7 +444,7 @@ __device__ __forceinline__ void touch_body(const BatchFrame* __restrict__ frames
     const int tiles_x = (p.ws + TT - 1) / TT;
     const int sx = (tile % tiles_x) * TT + (tid & (TT - 1));
     const int sy = (tile / tiles_x) * TT + (tid / TT);
-    const int f0 = grp * p.tf;
+    const int f0 = grp * p.tf;  // (the group's frames share a mask word: touch_group_frames)
     if (sx < p.ws && sy < p.hs) {
         const int r = sy * p.stride, c = sx * p.stride;
         for (int f = f0; f < f0 + p.tf && f < nframes; ++f) {
@@ -451,7 +481,7 @@ __device__ __forceinline__ void touch_body(const BatchFrame* __restrict__ frames
                 lo[k] = floor_div(q[k] - p.trunc, p.unit_len, p.inv_unit);
                 hi[k] = floor_div(q[k] + p.trunc, p.unit_len, p.inv_unit);
             }
-            const unsigned long long bit = 1ull << f;
+            const unsigned long long bit = 1ull << (WIDE ? f & 63 : f);
             for (int ux = lo[0]; ux <= hi[0]; ++ux)
                 for (int uy = lo[1]; uy <= hi[1]; ++uy)
                     for (int uz = lo[2]; uz <= hi[2]; ++uz) {
@@ -461,7 +491,8 @@ __device__ __forceinline__ void touch_body(const BatchFrame* __restrict__ frames
                         }
                         const unsigned long long key = pack_key(ux, uy, uz);
                         if (!unit_owned(d, key)) continue;
-                        if (!lds_merge(s_keys, s_masks, s_used, &s_nused, key, bit)) touch_unit_batch(d, f, p.slot_cap, p.pc, ux, uy, uz);
+                        if (!lds_merge(s_keys, s_masks, s_used, &s_nused, key, bit))
+                            touch_unit_batch<WIDE>(d, f, p.slot_cap, p.pc, ux, uy, uz);
                     }
         }
     }
@@ -484,7 +515,7 @@ __device__ __forceinline__ void touch_body(const BatchFrame* __restrict__ frames
                 // no read of the mask first: another frame group's workgroup set the unit's other bits, so the
                 // bits are almost never all present, and the read was one more dependent global round trip on
                 // every tile's chain (front end 112 -> 104 us per 64-frame batch, r05ax)
-                fresh = atomicOr(&d.fmask[slot], s_masks[e]) == 0ull;
+                fresh = touch_slot<WIDE>(d, slot, f0, s_masks[e]);
             }
         }
         int cnt;
@@ -503,11 +534,11 @@ __device__ __forceinline__ void touch_body(const BatchFrame* __restrict__ frames
     }
 }
 
-template <bool REPLAY>
+template <bool REPLAY, bool WIDE>
 __global__ __launch_bounds__(256) void k_batch_touch(const BatchFrame* __restrict__ frames, BatchTouchParams p,
                                                      TsdfDev d, int nframes) {
     __shared__ TouchLds lds;
-    touch_body<REPLAY>(frames, p, d, nframes, lds, (int)blockIdx.x, (int)blockIdx.y);
+    touch_body<REPLAY, !REPLAY, WIDE>(frames, p, d, nframes, lds, (int)blockIdx.x, (int)blockIdx.y);
 }
 // the split front end's touch (no staging paths compiled in: 69 instead of 96 VGPRs)
 __global__ __launch_bounds__(256) void k_batch_touch_split(const BatchFrame* __restrict__ frames, BatchTouchParams p,
@@ -548,7 +579,9 @@ __device__ inline int work_slot(TsdfDev& d, int n, bool live, bool heavy) {
     return heavy ? bh + rh : n - 1 - (bl + rl);
 }
 
-template <bool REPLAY>
+// WIDE: the batch has frames in both mask words (the host knows: more than WORD_FRAMES frames); else word 0 alone is
+// read and cleared -- nothing set the second word or the claim
+template <bool REPLAY, bool WIDE>
 // wcount: where the integrate reads the batch's work-list length (the pair counter itself, or -- with the front end
 // double-buffered -- a per-set copy, since the next batch's units kernel zeroes the other pair counter while this
 // batch's integrate may still run)
@@ -578,7 +611,8 @@ __global__ __launch_bounds__(256) void k_batch_units(TsdfDev d, UnitWork* __rest
         const int slot = live ? d.bslots[t] : 0;
         int id = live ? d.hvals[slot] : 0;
         // requested with the id, ahead of the allocation atomic (the compiler keeps loads behind an atomic)
-        const unsigned long long mask = live ? d.fmask[slot] : 0ull;
+        const unsigned long long mask = live ? d.fmask[(unsigned)slot * FMASK_STRIDE] : 0ull;
+        const unsigned long long mask1 = WIDE && live ? d.fmask[(unsigned)slot * FMASK_STRIDE + 1] : 0ull;
         const unsigned long long hkey = live ? d.hkeys[slot] : 0ull;
         int cnt;
         const int rank = wave_excl_count(live && id < 0, cnt);
@@ -594,9 +628,13 @@ __global__ __launch_bounds__(256) void k_batch_units(TsdfDev d, UnitWork* __rest
         // the integrate's workgroups (dispatched in item order) start the long items first and the short ones fill
         // the tail (8 sector ranks: 174 -> 165 us per batch).  A whole volume keeps the touch's order, whose
         // neighbouring units share staged pixels in L2 (heavy-first there: 715 -> 734 us per batch)
-        const int wpos = d.shard_world > 1 ? work_slot(d, n, live, __popcll(mask) >= WORK_HEAVY_FRAMES) : t;
+        const int wpos = d.shard_world > 1 ? work_slot(d, n, live, __popcll(mask) + __popcll(mask1) >= WORK_HEAVY_FRAMES) : t;
         if (!live) continue;
-        d.fmask[slot] = 0ull;
+        d.fmask[(unsigned)slot * FMASK_STRIDE] = 0ull;
+        if constexpr (WIDE) {
+            d.fmask[(unsigned)slot * FMASK_STRIDE + 1] = 0ull;
+            d.fmask[(unsigned)slot * FMASK_STRIDE + FMASK_CLAIM] = 0ull;
+        }
         int kx, ky, kz;
         unpack_key(hkey, kx, ky, kz);
         if (id <= -2) {
@@ -626,9 +664,9 @@ __global__ __launch_bounds__(256) void k_batch_units(TsdfDev d, UnitWork* __rest
         w.ky = ky;
         w.kz = kz;
         w.mask = mask;
-        w.pad = 0ull;
+        w.mask1 = mask1;
         work[wpos] = w;
-        if (id != -1) pairs += (unsigned long long)__popcll(mask);
+        if (id != -1) pairs += (unsigned long long)(__popcll(mask) + __popcll(mask1));
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -1105,7 +1143,8 @@ __device__ __forceinline__ void integrate_frames(const BatchFrame* __restrict__ 
     }
 }
 
-// The slice pre-test (slice_pretest.h), in the coarse item's prologue: lane f decides frame f of the item's mask from
+// The slice pre-test (slice_pretest.h), in the coarse item's prologue, once per non-empty mask word: lane f decides
+// frame fb + f of the batch (`frames` is the word's first frame, frame fb; `mask` the item's mask word) from
 // the slice's bounding box in that frame's image and the frame's tile-max depth map -- the map read through a buffer
 // resource over the whole set's maps, so a wrong index reads 0 or another tile and cannot fault -- and the ballot is the
 // frames in which no voxel of the slice can be a candidate.  Such a frame is one integrate_frames leaves at its idle
@@ -1113,7 +1152,7 @@ __device__ __forceinline__ void integrate_frames(const BatchFrame* __restrict__ 
 // decision.  Float64 and per-lane loops are fine here: once per item, before the voxel state is loaded.
 __device__ __forceinline__ unsigned long long pretest_idle(const BatchFrame* __restrict__ frames,
                                                            const IntegrateParams& p, const UnitWork& w, int s,
-                                                           unsigned long long mask) {
+                                                           int fb, unsigned long long mask) {
     // per-item copies of the lane index and the launch's constants: what derives from them alone (the frame's address,
     // float64 forms and products) would otherwise be computed before the item loop and kept through the frame loop,
     // which has no register to spare (they were spilled)
@@ -1129,7 +1168,7 @@ __device__ __forceinline__ unsigned long long pretest_idle(const BatchFrame* __r
     asm volatile("" : "+s"(in.W), "+s"(in.H));
     if ((mask >> f) & 1ull) {
         const __amdgpu_buffer_rsrc_t map = make_rsrc(p.tmax, (p.tmax_words + PRE_SLACK) * 4);
-        const int base = f * p.tmax_tiles;
+        const int base = (fb + f) * p.tmax_tiles;
         idle = slice_idle(frames[f].E, in, vl, unit_len, w.kx, w.ky, w.kz, s, trunc, [&](int i) {
             // (PRE_NONE: 2^30 bytes or more into a buffer of fewer: the range check answers zeros)
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(map, (base + i) * 4, 0, 0);
@@ -1142,12 +1181,14 @@ __device__ __forceinline__ unsigned long long pretest_idle(const BatchFrame* __r
 }
 
 // One work item: slice s (this wave's) of the unit of work entry w -- its ZB voxels per lane loaded (or zero for a
-// fresh unit), taken through the batch's frames of `mask` (w.mask, less the frames the pre-test dropped) and written
-// back.  ZB == 2: the fine slices (KT their pipeline's depth).
-template <bool C64, bool FAST, int ZB, int KT>
-__device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ frames, const IntegrateParams& p,
-                                               const TsdfDev& d, const UnitWork& w, unsigned long long mask, int s,
-                                               int npx, const float* s_r32, const double* s_r64, unsigned& upd) {
+// fresh unit), taken through the batch's frames of its WORDS mask words (w.mask, w.mask1, less the frames the pre-test
+// dropped) and written back: the state is loaded once, word 0's frames run, then word 1's (frames 64 ..., in call
+// order), and it is stored once.  ZB == 2: the fine slices (KT their pipeline's depth).
+template <bool C64, bool FAST, int ZB, int KT, int WORDS>
+__device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ batch, const IntegrateParams& p,
+                                               const TsdfDev& d, const UnitWork& w, unsigned long long mask0,
+                                               unsigned long long mask1, int s, int npx, const float* s_r32,
+                                               const double* s_r64, unsigned& upd) {
     using CT = typename std::conditional<C64, double, float>::type;
     const int ent = w.id;
     if (ent == -1) return;
@@ -1197,71 +1238,78 @@ __device__ __forceinline__ void integrate_item(const BatchFrame* __restrict__ fr
     const float py = (p.half + p.vl * (float)y) + oy;
     const float pz = p.half + oz;
     unsigned iu = 0;  // this item's updates
-    if constexpr (ZB == 2) {
-        // Frame pipeline (the fine slices serve batches with few units, whose waves cannot hide a frame's dependent
-        // gathers behind other waves: the wave's chain of frames IS the batch's time).  Every load of a frame is
-        // state-independent -- the projections and (depth, colour) gathers (frame_tap), the candidate test and the
-        // multiplier gather (voxel_candidate, voxel_multiplier) -- only the update (voxel_update) waits for it and reads
-        // the voxel state.  So frame f+KT's tap and frame f+KC's candidate stage are issued before frame f's update, from
-        // KT + 1 register slots (the loop is unrolled over the slots so every slot is a fixed register set: a
-        // rotating copy would wait for the loads in flight).  The updates still run in frame order with the same
-        // arithmetic: the bits are the unpipelined loop's.  KT = 1, KC = 0 is the round-5 one-frame skew.
-        // The pipeline stands here, not in a function of its own as the coarse loop does: with the voxel state passed
-        // by reference the float64-colour kernels took 6 more VGPRs and the fused fine launch ran 5 % slower.
-        constexpr int KC = KT - 1, RS = KT + 1;
-        unsigned long long mt = mask;  // frames not yet tapped
-        int fs[RS];                     // frame of each slot (wave-uniform), -1: past the last frame
-        int pixv[RS][ZB];
-        float pcz[RS][ZB], dv[RS][ZB], df[RS][ZB];
-        uint32_t cv[RS][ZB];
-        bool cand[RS][ZB];
-        unsigned mv[RS][ZB];
-        auto tap = [&](auto J) __attribute__((always_inline)) {
-            constexpr int j = decltype(J)::value;
-            if (mt) {
-                const int f = __ffsll((long long)mt) - 1;
-                mt &= mt - 1;
-                fs[j] = f;
-                frame_tap<ZB, false>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
-            } else {
-                fs[j] = -1;
-            }
-        };
-        auto stage_c = [&](auto J) __attribute__((always_inline)) {
-            constexpr int j = decltype(J)::value;
-            if (fs[j] < 0) return;
-            const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
+    // one frame loop, run once per non-empty mask word (the fused launches read one word)
+#pragma nounroll
+    for (int word = 0; word < WORDS; ++word) {
+        const unsigned long long mask = (WORDS > 1 && word) ? mask1 : mask0;
+        if (WORDS > 1 && !mask) continue;
+        const BatchFrame* frames = batch + word * WORD_FRAMES;  // the word's first frame
+        if constexpr (ZB == 2) {
+            // Frame pipeline (the fine slices serve batches with few units, whose waves cannot hide a frame's dependent
+            // gathers behind other waves: the wave's chain of frames IS the batch's time).  Every load of a frame is
+            // state-independent -- the projections and (depth, colour) gathers (frame_tap), the candidate test and the
+            // multiplier gather (voxel_candidate, voxel_multiplier) -- only the update (voxel_update) waits for it and reads
+            // the voxel state.  So frame f+KT's tap and frame f+KC's candidate stage are issued before frame f's update, from
+            // KT + 1 register slots (the loop is unrolled over the slots so every slot is a fixed register set: a
+            // rotating copy would wait for the loads in flight).  The updates still run in frame order with the same
+            // arithmetic: the bits are the unpipelined loop's.  KT = 1, KC = 0 is the round-5 one-frame skew.
+            // The pipeline stands here, not in a function of its own as the coarse loop does: with the voxel state passed
+            // by reference the float64-colour kernels took 6 more VGPRs and the fused fine launch ran 5 % slower.
+            constexpr int KC = KT - 1, RS = KT + 1;
+            unsigned long long mt = mask;  // frames not yet tapped
+            int fs[RS];                     // frame of each slot (wave-uniform), -1: past the last frame
+            int pixv[RS][ZB];
+            float pcz[RS][ZB], dv[RS][ZB], df[RS][ZB];
+            uint32_t cv[RS][ZB];
+            bool cand[RS][ZB];
+            unsigned mv[RS][ZB];
+            auto tap = [&](auto J) __attribute__((always_inline)) {
+                constexpr int j = decltype(J)::value;
+                if (mt) {
+                    const int f = __ffsll((long long)mt) - 1;
+                    mt &= mt - 1;
+                    fs[j] = f;
+                    frame_tap<ZB, false>(frames[f], p, npx, px, py, pz, z0, pixv[j], pcz[j], dv[j], cv[j]);
+                } else {
+                    fs[j] = -1;
+                }
+            };
+            auto stage_c = [&](auto J) __attribute__((always_inline)) {
+                constexpr int j = decltype(J)::value;
+                if (fs[j] < 0) return;
+                const __amdgpu_buffer_rsrc_t mult_rsrc = make_rsrc(p.mult, npx * 4);
 #pragma unroll
-            for (int k = 0; k < ZB; ++k) {  // test and gather voxel by voxel: no frame is left early here
-                cand[j][k] = voxel_candidate<false>(p, pixv[j][k], pcz[j][k], dv[j][k], df[j][k]);
-                mv[j][k] = voxel_multiplier<false>(mult_rsrc, pixv[j][k], cand[j][k]);
-            }
-        };
-        auto stage_d = [&](auto J) __attribute__((always_inline)) -> bool {
-            constexpr int j = decltype(J)::value;
-            if (fs[j] < 0) return false;
-            const bool use_color = frames[fs[j]].color != nullptr;
+                for (int k = 0; k < ZB; ++k) {  // test and gather voxel by voxel: no frame is left early here
+                    cand[j][k] = voxel_candidate<false>(p, pixv[j][k], pcz[j][k], dv[j][k], df[j][k]);
+                    mv[j][k] = voxel_multiplier<false>(mult_rsrc, pixv[j][k], cand[j][k]);
+                }
+            };
+            auto stage_d = [&](auto J) __attribute__((always_inline)) -> bool {
+                constexpr int j = decltype(J)::value;
+                if (fs[j] < 0) return false;
+                const bool use_color = frames[fs[j]].color != nullptr;
 #pragma unroll
-            for (int k = 0; k < ZB; ++k)
-                voxel_update<C64, FAST>(cand[j][k], df[j][k] * __uint_as_float(mv[j][k]), cv[j][k], use_color, p, s_r32,
-                                        s_r64, ts[k], wt[k], cr[k], cg[k], cb[k], iu);
-            return true;
-        };
-        // one iteration = frame f in slot J: the candidate stage of f + KC, the tap of f + KT (into the slot frame f - 1
-        // left), the update of f
-        auto iter = [&](auto J) __attribute__((always_inline)) -> bool {
-            constexpr int j = decltype(J)::value;
-            stage_c(std::integral_constant<int, (j + KC) % RS>{});
-            tap(std::integral_constant<int, (j + KT) % RS>{});
-            return stage_d(J);
-        };
-        // prologue: taps of the first KT frames, candidate stages of the first KC
-        static_for<KT>(tap);
-        static_for<KC>(stage_c);
-        while (static_all<RS>(iter)) {
-        }
-    } else
-        integrate_frames<C64, FAST, ZB>(frames, p, npx, mask, px, py, pz, z0, s_r32, s_r64, ts, wt, cr, cg, cb, iu);
+                for (int k = 0; k < ZB; ++k)
+                    voxel_update<C64, FAST>(cand[j][k], df[j][k] * __uint_as_float(mv[j][k]), cv[j][k], use_color, p, s_r32,
+                                            s_r64, ts[k], wt[k], cr[k], cg[k], cb[k], iu);
+                return true;
+            };
+            // one iteration = frame f in slot J: the candidate stage of f + KC, the tap of f + KT (into the slot frame f - 1
+            // left), the update of f.  The pipeline drains at the end of a mask word.
+            auto iter = [&](auto J) __attribute__((always_inline)) -> bool {
+                constexpr int j = decltype(J)::value;
+                stage_c(std::integral_constant<int, (j + KC) % RS>{});
+                tap(std::integral_constant<int, (j + KT) % RS>{});
+                return stage_d(J);
+            };
+            // prologue: taps of the first KT frames, candidate stages of the first KC
+            static_for<KT>(tap);
+            static_for<KC>(stage_c);
+            while (static_all<RS>(iter)) {
+            }
+        } else
+            integrate_frames<C64, FAST, ZB>(frames, p, npx, mask, px, py, pz, z0, s_r32, s_r64, ts, wt, cr, cg, cb, iu);
+    }
     upd += iu;
     // a slice none of whose voxels updated in this batch still holds its HBM values (fresh ones: zeros)
     if (!fresh && !__any(iu != 0u)) return;
@@ -1320,7 +1368,9 @@ struct RcpLds {
 // building the reciprocal table -- for a batch of few units (a spatial shard) the idle workgroups' tables had cost
 // more than the integrate itself (r05e: a 1/8 shard's 64-frame batch 165-200 us whatever its slicing)
 // PRE: the launch of its own with coarse slices runs the slice pre-test when the batch has tile-max maps (p.tmax).
-template <bool C64, bool FAST, int ZB, int KT, bool HEAVY, int WG, bool PRE = false>
+// WORDS: the mask words an item reads: FMASK_WORDS for the launch of its own (a whole volume's Direct batch has up to
+// MAX_BATCH frames), 1 for the fused launches (their batches keep WORD_FRAMES).
+template <bool C64, bool FAST, int ZB, int KT, bool HEAVY, int WG, bool PRE = false, int WORDS = 1>
 __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ frames, const IntegrateParams& p,
                                                const TsdfDev& d, const UnitWork* __restrict__ work,
                                                const int* __restrict__ wcount, float* s_r32, double* s_r64, int bid,
@@ -1343,7 +1393,7 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
     const int n = *wcount;
     const int nh = HEAVY ? wcount[2] : 0;  // heavy units first; the rest are stored back to front (k_batch_units)
     const int npx = p.W * p.H;
-    unsigned upd = 0;  // per lane: <= ZB voxels x 64 frames x units per workgroup, far below 2^32
+    unsigned upd = 0;  // per lane: <= ZB voxels x MAX_BATCH frames x units per workgroup, far below 2^32
     unsigned dropped = 0;  // wave-uniform: wave-frames the pre-test dropped
     const int items = PARTS == 1 ? n : ((n + 7) / 8) * 8 * PARTS;
     for (int it = bid; it < items; it += nblk) {
@@ -1352,16 +1402,23 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
         const int part = PARTS == 1 ? 0 : (it >> 3) % PARTS;
         const int s = part * WG + wave;  // slice of this wave
         const UnitWork& w = work[!HEAVY || u < nh ? u : n - 1 - (u - nh)];
-        unsigned long long mask = w.mask;
+        unsigned long long mask0 = w.mask, mask1 = WORDS > 1 ? w.mask1 : 0ull;
         if constexpr (PRE) {
             if (p.tmax && w.id != -1) {  // wave-uniform
-                const unsigned long long idle = pretest_idle(frames, p, w, s, mask);
-                mask &= ~idle;
-                dropped += (unsigned)__popcll(idle);
-                if (!mask && w.id >= 0) continue;  // (a fresh unit still writes its zeros)
+#pragma nounroll
+                for (int word = 0; word < WORDS; ++word) {
+                    const unsigned long long mask = word ? mask1 : mask0;
+                    if (!mask) continue;
+                    const unsigned long long idle =
+                        pretest_idle(frames + word * WORD_FRAMES, p, w, s, word * WORD_FRAMES, mask);
+                    if (word) mask1 &= ~idle;
+                    else mask0 &= ~idle;
+                    dropped += (unsigned)__popcll(idle);
+                }
+                if (!(mask0 | mask1) && w.id >= 0) continue;  // (a fresh unit still writes its zeros)
             }
         }
-        integrate_item<C64, FAST, ZB, KT>(frames, p, d, w, mask, s, npx, s_r32, s_r64, upd);
+        integrate_item<C64, FAST, ZB, KT, WORDS>(frames, p, d, w, mask0, mask1, s, npx, s_r32, s_r64, upd);
     }
     const unsigned long long tot = wave_sum((unsigned long long)upd);
     if ((threadIdx.x & 63) == 0 && tot)
@@ -1376,13 +1433,14 @@ __device__ __forceinline__ void integrate_body(const BatchFrame* __restrict__ fr
 // The reciprocal table is the launch's dynamic LDS: rcp_hi + 1 entries of the kernel's precision (integrate_form), so a
 // CU holds as many one-wave workgroups as it has wave slots until the table passes 5 KiB.
 extern __shared__ double s_rcp_dyn[];
-template <bool C64, bool FAST, int ZB = BZ, int KT = 1, int WG = INT_WG>
+// WORDS: the batch's mask words (2 only for a batch of more than WORD_FRAMES frames: integrate_form)
+template <bool C64, bool FAST, int ZB = BZ, int KT = 1, int WG = INT_WG, int WORDS = 1>
 __global__ __launch_bounds__(64 * WG, (C64 && !FAST) ? 5 : (ZB == 2 ? 4 : INT_WAVES_PER_EU)) void k_batch_integrate(
     const BatchFrame* __restrict__ frames, IntegrateParams p, TsdfDev d, const UnitWork* __restrict__ work,
     const int* __restrict__ wcount) {
-    integrate_body<C64, FAST, ZB, KT, false, WG, ZB == BZ>(frames, p, d, work, wcount,
-                                                           reinterpret_cast<float*>(s_rcp_dyn), s_rcp_dyn,
-                                                           (int)blockIdx.x, (int)gridDim.x);
+    integrate_body<C64, FAST, ZB, KT, false, WG, ZB == BZ, WORDS>(frames, p, d, work, wcount,
+                                                                  reinterpret_cast<float*>(s_rcp_dyn), s_rcp_dyn,
+                                                                  (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The deferred integrate of a sharded volume's batch k and the touch of batch k + 1 in ONE launch (round 6): workgroups
@@ -1517,29 +1575,28 @@ constexpr int INT_FINE_KT = 1;
 // workgroup's place on the CU only when the slowest wave ends, so the smaller the workgroup the sooner the dispatcher
 // refills the slot.  The fine slices and the fused launches keep INT_WG waves.
 constexpr int INT_WG_DEFAULT = 1;
-template <int WG>
-static const void* coarse_kernel(int variant) {
-    static const void* const k[4] = {
-        (const void*)k_batch_integrate<false, false, BZ, 1, WG>, (const void*)k_batch_integrate<false, true, BZ, 1, WG>,
-        (const void*)k_batch_integrate<true, false, BZ, 1, WG>, (const void*)k_batch_integrate<true, true, BZ, 1, WG>};
+template <int ZB, int KT, int WG, int WORDS>
+static const void* integrate_kernels(int variant) {
+    static const void* const k[4] = {(const void*)k_batch_integrate<false, false, ZB, KT, WG, WORDS>,
+                                     (const void*)k_batch_integrate<false, true, ZB, KT, WG, WORDS>,
+                                     (const void*)k_batch_integrate<true, false, ZB, KT, WG, WORDS>,
+                                     (const void*)k_batch_integrate<true, true, ZB, KT, WG, WORDS>};
     return k[variant & 3];
 }
-// wg: waves per workgroup of a coarse variant (1, 2 or 4); the fine variants have INT_WG
-static const void* integrate_kernel(int variant, int wg) {
-    static const void* const k[16] = {
-        (const void*)k_batch_integrate<false, false, 2, 1>, (const void*)k_batch_integrate<false, true, 2, 1>,
-        (const void*)k_batch_integrate<true, false, 2, 1>, (const void*)k_batch_integrate<true, true, 2, 1>,
-        nullptr, nullptr, nullptr, nullptr,
-        (const void*)k_batch_integrate<false, false, 2, 2>, (const void*)k_batch_integrate<false, true, 2, 2>,
-        (const void*)k_batch_integrate<true, false, 2, 2>, (const void*)k_batch_integrate<true, true, 2, 2>,
-        nullptr, nullptr, nullptr, nullptr};
-    static const void* const k3[4] = {
-        (const void*)k_batch_integrate<false, false, 2, 3>, (const void*)k_batch_integrate<false, true, 2, 3>,
-        (const void*)k_batch_integrate<true, false, 2, 3>, (const void*)k_batch_integrate<true, true, 2, 3>};
+// wg: waves per workgroup of a coarse variant (1, 2 or 4); the fine variants have INT_WG.  words: the batch's mask words
+template <int WORDS>
+static const void* integrate_kernel_w(int variant, int wg) {
     if (!(variant & 4))
-        return wg == 1 ? coarse_kernel<1>(variant) : wg == 2 ? coarse_kernel<2>(variant) : coarse_kernel<4>(variant);
-    if (((variant >> 3) & 3) == 2) return k3[variant & 3];
-    return k[(variant & 3) + 8 * ((variant >> 3) & 1)];
+        return wg == 1   ? integrate_kernels<BZ, 1, 1, WORDS>(variant)
+               : wg == 2 ? integrate_kernels<BZ, 1, 2, WORDS>(variant)
+                         : integrate_kernels<BZ, 1, 4, WORDS>(variant);
+    const int kt = ((variant >> 3) & 3) + 1;
+    return kt == 3   ? integrate_kernels<2, 3, INT_WG, WORDS>(variant)
+           : kt == 2 ? integrate_kernels<2, 2, INT_WG, WORDS>(variant)
+                     : integrate_kernels<2, 1, INT_WG, WORDS>(variant);
+}
+static const void* integrate_kernel(int variant, int wg, int words) {
+    return words > 1 ? integrate_kernel_w<FMASK_WORDS>(variant, wg) : integrate_kernel_w<1>(variant, wg);
 }
 
 // LDS of a launch: the table's entries 0 .. rcp_hi in the variant's precision (the hardware allocates whole granules)
@@ -1554,15 +1611,15 @@ static unsigned rcp_lds_bytes(int variant, int rcp_hi) {
 // Co-resident workgroups of an integrate kernel on the device, by its waves per workgroup and its dynamic LDS in whole
 // granules (cached per device, kernel and size; a benign race at worst computes the same value twice).  0: the query
 // failed.
-static int integrate_resident(int variant, int wg, unsigned lds) {
-    static int cache[32][3][RCP_LDS_MAX + 1][64] = {};
+static int integrate_resident(int variant, int wg, unsigned lds, int words = 1) {
+    static int cache[2][32][3][RCP_LDS_MAX + 1][64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
     const unsigned granules = std::min((lds + LDS_GRANULE - 1) / LDS_GRANULE, RCP_LDS_MAX);
-    int* c = &cache[variant & 31][wg == 1 ? 0 : wg == 2 ? 1 : 2][granules][dev];
+    int* c = &cache[words > 1][variant & 31][wg == 1 ? 0 : wg == 2 ? 1 : 2][granules][dev];
     if (!*c) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, integrate_kernel(variant, wg), 64 * wg,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, integrate_kernel(variant, wg, words), 64 * wg,
                                                          granules * LDS_GRANULE) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu <= 0 ||
             cus <= 0)
@@ -1589,18 +1646,18 @@ struct IntForm {
     int wg, grid;
     unsigned lds;
 };
-static IntForm integrate_form(int variant, int rcp_hi) {
+static IntForm integrate_form(int variant, int rcp_hi, int words) {
     IntForm f;
     f.lds = rcp_lds_bytes(variant, rcp_hi);
     f.wg = INT_WG;
     if (!(variant & 4)) {
-        const int want = integrate_resident(variant, INT_WG, f.lds) * INT_WG;  // waves
+        const int want = integrate_resident(variant, INT_WG, f.lds, words) * INT_WG;  // waves
         const int forced = g_tsdf_hooks.int_wg;  // otx_integrate_workgroup: 1, 2 or 4 at every table size
         f.wg = forced > 0 ? forced : INT_WG_DEFAULT;
-        while (forced <= 0 && f.wg < INT_WG && integrate_resident(variant, f.wg, f.lds) * f.wg < want) f.wg *= 2;
+        while (forced <= 0 && f.wg < INT_WG && integrate_resident(variant, f.wg, f.lds, words) * f.wg < want) f.wg *= 2;
     }
-    f.fn = integrate_kernel(variant, f.wg);
-    const int r = integrate_resident(variant, f.wg, f.lds);
+    f.fn = integrate_kernel(variant, f.wg, words);
+    const int r = integrate_resident(variant, f.wg, f.lds, words);
     f.grid = r ? r * INT_GRID_MULT : 4096 * (INT_WG / f.wg);
     return f;
 }
@@ -1664,7 +1721,7 @@ static bool tmask_fits(int w, int h) {
 }
 static ot_status ensure_tmask(ot_tsdf* vol, int w, int h, hipStream_t stream) {
     if (vol->tmask && vol->tmask_w == w && vol->tmask_h == h) return OT_OK;
-    const int64_t words = (int64_t)MAX_BATCH * SM_PARTS * ((h + STY - 1) / STY) * (((w + STX - 1) / STX + 31) / 32);
+    const int64_t words = (int64_t)WORD_FRAMES * SM_PARTS * ((h + STY - 1) / STY) * (((w + STX - 1) / STX + 31) / 32);
     if (vol->tmask) {
         OT_HIP_TRY(hipStreamSynchronize(stream));
         OT_HIP_TRY(hipFree(vol->tmask));
@@ -1693,6 +1750,23 @@ static bool defer_on(const ot_tsdf* vol, bool split) {
     const int hook = g_tsdf_hooks.defer;
     if (!split || hook == 0 || vol->overlap_mode > 0) return false;
     return hook > 0 || vol->dev.shard_world >= 4;
+}
+
+// Frames per batch of the volume as it is set now: ot_tsdf_set_batch's count, at most MAX_BATCH for a whole volume whose
+// batches run BatchMode::Direct with the full staging, at most WORD_FRAMES for every other -- a sharded volume, the
+// double-buffered front end, the split front end and the deferred integrate (which needs the split) read one mask word.
+// tsdf_flush, the integrate calls' auto-flush and the staging buffers' sizes all ask here; integrate_batch refuses a
+// longer batch than its plan reads.
+static int batch_cap(const ot_tsdf* vol) {
+    const bool wide = vol->dev.shard_world <= 1 && !overlap_on(vol) && !split_on(vol);
+    return std::min(vol->batch_max, wide ? MAX_BATCH : WORD_FRAMES);
+}
+// Frames a staging buffer of the volume is sized for when a batch of n frames finds it too small: the batch itself, the
+// volume's cap once a batch has passed WORD_FRAMES, and otherwise no more than WORD_FRAMES -- a volume that is flushed
+// every 64 frames or fewer (an object's) never pays for 128 frames of staging (315 MB at 640 x 480).
+static int64_t staging_frames(const ot_tsdf* vol, int n) {
+    const int cap = batch_cap(vol);
+    return std::max(n, n > WORD_FRAMES ? cap : std::min(cap, WORD_FRAMES));
 }
 
 // order `stream` after the last batch's integrate when it ran on the volume's integrate stream
@@ -1762,7 +1836,7 @@ static ot_status grow_pool(ot_tsdf* vol, int64_t need, int n_used, hipStream_t s
         (e = alloc((void**)&nsorted, sizeof(unsigned) * nmax, 2)) == hipSuccess &&
         (e = alloc((void**)&nd.hkeys, sizeof(unsigned long long) * cap, 3)) == hipSuccess &&
         (e = alloc((void**)&nd.hvals, sizeof(int) * cap, 4)) == hipSuccess &&
-        (e = alloc((void**)&nd.fmask, sizeof(unsigned long long) * cap, 5)) == hipSuccess &&
+        (e = alloc((void**)&nd.fmask, fmask_bytes(cap), 5)) == hipSuccess &&
         (e = alloc((void**)&nd.bslots, sizeof(int) * cap, 6)) == hipSuccess &&
         (e = alloc((void**)&nd.work, sizeof(UnitWork) * cap, 7)) == hipSuccess &&
         (!vol->bset[1].work || (e = alloc(&work1, sizeof(UnitWork) * cap, 8)) == hipSuccess)) {
@@ -1783,7 +1857,7 @@ static ot_status grow_pool(ot_tsdf* vol, int64_t need, int n_used, hipStream_t s
     }
     OT_HIP_TRY(hipMemsetAsync(nd.hkeys, 0xFF, sizeof(unsigned long long) * cap, stream));
     OT_HIP_TRY(hipMemsetAsync(nd.hvals, 0xFF, sizeof(int) * cap, stream));
-    OT_HIP_TRY(hipMemsetAsync(nd.fmask, 0, sizeof(unsigned long long) * cap, stream));
+    OT_HIP_TRY(hipMemsetAsync(nd.fmask, 0, fmask_bytes(cap), stream));
     nd.hash_mask = (int)(cap - 1);
     nd.max_units = (int)nmax;
     if (n_used > 0) hipLaunchKernelGGL(k_rehash, dim3((unsigned)((n_used + 255) / 256)), dim3(256), 0, stream, nd, n_used);
@@ -1913,14 +1987,20 @@ static void launch_front_end(ot_tsdf* vol, const BatchCtx& bc, bool replay, bool
     BatchTouchParams tp = bc.tp;
     tp.slot_cap = (int)vol->hash_cap;  // (a replay's hash has grown)
     if (touch) {  // the staging-only workgroups (stage_blocks > 0) belong to the first pass of an unsplit batch
-        const auto touch_k = replay ? k_batch_touch<true> : plan.split ? k_batch_touch_split : k_batch_touch<false>;
+        const bool wide = bc.n > WORD_FRAMES;  // (never split: integrate_batch)
+        const auto touch_k = replay       ? (wide ? k_batch_touch<true, true> : k_batch_touch<true, false>)
+                             : plan.split ? k_batch_touch_split
+                             : wide       ? k_batch_touch<false, true>
+                                          : k_batch_touch<false, false>;
         const unsigned tiles = (unsigned)tp.tiles + (replay ? 0u : (unsigned)std::max(0, tp.stage_blocks));
         hipLaunchKernelGGL(touch_k, dim3(tiles, (unsigned)((bc.n + tp.tf - 1) / tp.tf)), dim3(256), 0, stream, bf, tp,
                            vol->dev, bc.n);
     }
     const bool missing_only = replay && plan.mode != BatchMode::Deferred;
     int* wcopy = missing_only ? nullptr : plan.wcopy;
-    const auto units_k = missing_only ? k_batch_units<true> : k_batch_units<false>;
+    const bool wide_units = bc.n > WORD_FRAMES;
+    const auto units_k = missing_only ? (wide_units ? k_batch_units<true, true> : k_batch_units<true, false>)
+                                      : (wide_units ? k_batch_units<false, true> : k_batch_units<false, false>);
     hipLaunchKernelGGL(units_k, dim3(256), dim3(256), 0, stream, vol->dev, work, bc.pc, vol->hmail + OT_MAIL_WORDS, wcopy,
                        ++vol->units_seq);
     if (plan.split)  // (a replay: from the caller's frames, valid until this flush returns)
@@ -1933,7 +2013,7 @@ static ot_status launch_integrate(ot_tsdf* vol, const BatchCtx& bc, int variant,
     const BatchFrame* bf = vol->bset[bc.plan.set].bframes;
     const UnitWork* uw = (const UnitWork*)set_work(vol, bc.plan.set);
     void* args[] = {(void*)&bf, (void*)&bc.ip0, (void*)&vol->dev, (void*)&uw, (void*)&wcount};
-    const IntForm f = integrate_form(variant, bc.ip0.rcp_hi);
+    const IntForm f = integrate_form(variant, bc.ip0.rcp_hi, bc.n > WORD_FRAMES ? FMASK_WORDS : 1);
     OT_HIP_TRY(hipLaunchKernel(f.fn, dim3(f.grid), dim3(64 * f.wg), args, f.lds, stream));
     OT_LAUNCH_CHECK();
     return OT_OK;
@@ -2046,6 +2126,8 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
     bc.n = n;
     if ((st = plan_batch(vol, in, bc.pc, bc.plan)) != OT_OK) return st;
     const BatchPlan& plan = bc.plan;
+    if (n > MAX_BATCH || (n > WORD_FRAMES && (plan.mode != BatchMode::Direct || plan.split)))
+        return fail(OT_ERR_INVALID_ARGUMENT, "[ScalableTSDFVolume::Integrate] batch longer than its plan's frame masks");
     // A pending deferred batch is handed over here, before anything below restages a set.  On another stream than its
     // front end's, this stream first waits for that one: this batch's set was last integrated there, inside the launch
     // with the deferred batch's touch (queued before its units kernel).  And a batch that does not fuse with it (the mode changed: the hooks, the overlap
@@ -2067,7 +2149,7 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
             OT_HIP_TRY(hipFree(bs.bdc));
             bs.bdc = nullptr;
         }
-        const int64_t cap = npx * std::max(n, std::min(vol->batch_max, MAX_BATCH));
+        const int64_t cap = npx * staging_frames(vol, n);
         OT_HIP_TRY(hipMalloc(&bs.bdc, sizeof(uint2) * cap));
         bs.cap = cap;
     }
@@ -2079,6 +2161,7 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
     hipLaunchKernelGGL(k_copy_frames, dim3(1), dim3(COPY_FRAMES_LANES), 0, stream, (const uint4*)host,
                        (uint4*)bs.bframes, (int)(sizeof(BatchFrame) / 16) * n);
     bc.tp = make_touch_params(vol, in, bc.pc, plan.split);
+    bc.tp.tf = touch_group_frames(bc.tp.tf, n);
     if (plan.pretest) {  // the set's tile-max maps: written by this batch's staging, read by its integrate and a replay's
         const int64_t tiles = (int64_t)pre_tiles(in.width) * pre_tiles(in.height);
         if (bs.tmax_cap < tiles * n) {
@@ -2088,7 +2171,7 @@ static ot_status integrate_batch(ot_tsdf* vol, const PendingFrame* frames, int n
                 OT_HIP_TRY(hipFree(bs.tmax));
                 bs.tmax = nullptr, bs.tmax_cap = 0;
             }
-            const int64_t cap = tiles * std::max(n, std::min(vol->batch_max, MAX_BATCH));
+            const int64_t cap = tiles * staging_frames(vol, n);
             OT_HIP_TRY(hipMalloc(&bs.tmax, sizeof(unsigned) * (cap + PRE_SLACK)));
             bs.tmax_cap = cap;
         }
@@ -2183,9 +2266,9 @@ ot_status tsdf_flush(ot_tsdf* vol, hipStream_t stream, bool join) {
     // the volume changes: the last extractions' structures are stale
     if (!frames.empty()) vol->mesh.valid = vol->cloud.valid = false;
     while (i < frames.size()) {
-        // a batch: consecutive frames with identical intrinsics, at most batch_max (<= 64)
+        // a batch: consecutive frames with identical intrinsics, at most batch_cap (<= MAX_BATCH)
         size_t n = 1;
-        const int cap = std::min(vol->batch_max, MAX_BATCH);
+        const int cap = batch_cap(vol);
         while (i + n < frames.size() && (int)n < cap &&
                std::memcmp(&frames[i + n].intr, &frames[i].intr, sizeof(ot_intrinsics)) == 0)
             ++n;
@@ -2219,7 +2302,7 @@ ot_status ot_tsdf_integrate(ot_tsdf* vol, const float* depth, const uint8_t* col
     f.depth_trunc = 0.0;
     vol->pending.push_back(f);
     // a full queue is integrated; the integrate may keep running on the volume's integrate stream (overlap mode)
-    if ((int)vol->pending.size() >= std::min(vol->batch_max, MAX_BATCH)) return tsdf_flush(vol, S(stream), false);
+    if ((int)vol->pending.size() >= batch_cap(vol)) return tsdf_flush(vol, S(stream), false);
     return OT_OK;
 }
 
@@ -2236,7 +2319,7 @@ ot_status ot_tsdf_integrate_u16(ot_tsdf* vol, const uint16_t* depth, const uint8
     f.depth_scale = depth_scale;
     f.depth_trunc = depth_trunc;
     vol->pending.push_back(f);
-    if ((int)vol->pending.size() >= std::min(vol->batch_max, MAX_BATCH)) return tsdf_flush(vol, S(stream), false);
+    if ((int)vol->pending.size() >= batch_cap(vol)) return tsdf_flush(vol, S(stream), false);
     return OT_OK;
 }
 
@@ -2251,6 +2334,11 @@ ot_status ot_tsdf_integrate_u16_frames(ot_tsdf* vol, int32_t n, const uint16_t* 
                                              in, extrinsics + 16 * (size_t)k, depth_scale, depth_trunc, stream);
         if (st != OT_OK) return st;
     }
+    // A scan handed over in one call does not wait for the next reader: what the call leaves queued starts now once it
+    // is as long as a one-word batch (the frames that, frame by frame under a cap of WORD_FRAMES, had started at the
+    // 64th call), so the host's work up to the reader runs beside the integrate -- an object's 64-frame scan under the
+    // default cap of 128.  Fewer frames stay queued for the calls that follow.
+    if ((int)vol->pending.size() >= std::min(vol->batch_max, WORD_FRAMES)) return tsdf_flush(vol, S(stream), false);
     return OT_OK;
 }
 

@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void k_tsdf_clear(TsdfDev d, int64_t cap) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += (int64_t)gridDim.x * 256) {
         d.hkeys[i] = ~0ull;
         d.hvals[i] = -1;
-        d.fmask[i] = 0ull;
+        for (int k = 0; k < FMASK_STRIDE; ++k) d.fmask[i * FMASK_STRIDE + k] = 0ull;
     }
     if (blockIdx.x == 0) {
         if (threadIdx.x < N_COUNTERS) d.counters[threadIdx.x] = 0;
@@ -148,7 +148,7 @@ ot_status ot_tsdf_create(double voxel_length, double sdf_trunc, int32_t color_ty
     d.unit_floats = v->color64 ? UNIT_FLOATS_C64 : UNIT_FLOATS;
     if ((e = hipMalloc(&d.vox, sizeof(float) * (size_t)d.unit_floats * max_units)) != hipSuccess) return cleanup(e);
     if ((e = hipMalloc(&v->sorted_ids, sizeof(unsigned) * max_units)) != hipSuccess) return cleanup(e);
-    if ((e = hipMalloc(&d.fmask, sizeof(unsigned long long) * cap)) != hipSuccess) return cleanup(e);
+    if ((e = hipMalloc(&d.fmask, fmask_bytes(cap))) != hipSuccess) return cleanup(e);
     if ((e = hipMalloc(&d.bslots, sizeof(int) * cap)) != hipSuccess) return cleanup(e);
     if ((e = hipMalloc(&d.work, sizeof(UnitWork) * cap)) != hipSuccess) return cleanup(e);
     if ((e = hipMalloc(&v->bset[0].bframes, sizeof(BatchFrame) * MAX_BATCH)) != hipSuccess) return cleanup(e);
@@ -204,7 +204,7 @@ ot_status ot_tsdf_reset(ot_tsdf* v) {
     v->last_set = -1;
     OT_HIP_TRY(hipMemset(d.hkeys, 0xFF, sizeof(unsigned long long) * v->hash_cap));
     OT_HIP_TRY(hipMemset(d.hvals, 0xFF, sizeof(int) * v->hash_cap));
-    OT_HIP_TRY(hipMemset(d.fmask, 0, sizeof(unsigned long long) * v->hash_cap));
+    OT_HIP_TRY(hipMemset(d.fmask, 0, fmask_bytes(v->hash_cap)));
     OT_HIP_TRY(hipMemset(d.counters, 0, sizeof(int) * N_COUNTERS));
     OT_HIP_TRY(hipMemset(d.stats, 0, sizeof(unsigned long long) * N_STATS));
     OT_HIP_TRY(hipDeviceSynchronize());
@@ -417,9 +417,10 @@ ot_status otx_touch_stage_blocks(int32_t blocks) {
     return OT_OK;
 }
 
-// test hook: frames per touch workgroup (1..64, default TF): A/B timing and the parity of other groupings
+// test hook: frames per touch workgroup (1..64, default TF): A/B timing and the parity of other groupings.  A group never
+// crosses a mask word (tsdf.hip touch_group_frames), whatever the count
 ot_status otx_touch_frames(int32_t tf) {
-    if (tf < 1 || tf > MAX_BATCH) return fail(OT_ERR_INVALID_ARGUMENT, "otx_touch_frames: 1..64");
+    if (tf < 1 || tf > WORD_FRAMES) return fail(OT_ERR_INVALID_ARGUMENT, "otx_touch_frames: 1..64");
     g_tsdf_hooks.touch_tf = tf;
     return OT_OK;
 }

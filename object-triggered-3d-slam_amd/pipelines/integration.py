@@ -29,7 +29,8 @@ class ScalableTSDFVolume:
     Like Open3D's, the volume is unbounded: its block pool grows when a batch needs more units (records copied,
     keys rehashed, the batch's dropped units integrated again from its staged frames: the same volume bit for bit).
     Extra keyword arguments (not in Open3D): `max_units` (initial block-pool capacity in HBM), `batch_frames`
-    (frames queued per fused integration launch, default and max 64; 1 = integrate immediately; results are
+    (frames queued per fused integration launch, default and max 128 -- 64 for a sharded volume; 1 = integrate
+    immediately; results are
     bit-identical for any value: a batch applies its frames to each voxel in call order) and `color_precision`
     (64, the default: the running colour mean in float64 with exact division, Open3D's TSDFVoxel::color_ --
     bit-exact colours; 32: float32 state with one reciprocal per update, |rel| <= 1e-4, faster)."""
