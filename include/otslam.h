@@ -200,6 +200,32 @@ ot_status ot_registration_icp(const double* src, int64_t n, const double* tgt, i
                               int32_t max_iteration, double T_out_host[16], double* fitness_host, double* rmse_host,
                               int32_t* corr, int64_t* n_corr_host, int32_t* iterations_host, void* stream);
 
+/* pipelines.registration.compute_fpfh_feature(input, search_param) ("features"): per point the 33-bin
+ * Fast Point Feature Histogram over the neighbour list of ot_estimate_covariances (ascending (d2, index), the first
+ * min(knn, n), hybrid: of these the ones with d2 < radius^2; radius == 0: pure KNN).  Entry 0 of a list is skipped as
+ * "the query itself".  SPFH: per remaining entry the three Darboux pair features, each binned into 11 bins with
+ * weight 100 / (len - 1), added in list order.  FPFH: the neighbours' SPFH rows weighted by 1 / d2 (entries with
+ * d2 == 0 skipped), each block of 11 scaled to sum 100, plus the point's own SPFH.  Everything is float64, every
+ * operation rounded on its own.  xyz, normals: device [n][3]; fpfh_out: device [n][33], point-major; spfh_out
+ * (nullable): device [n][33], receives the SPFH.  knn must lie in 1..128 and radius must not be NaN
+ * (OT_ERR_INVALID_ARGUMENT, checked before any device work); n == 0 returns at once. */
+ot_status ot_compute_fpfh_feature(const double* xyz, const double* normals, int64_t n, int32_t knn, double radius,
+                                  double* fpfh_out /* n x 33, point-major */, double* spfh_out /* optional */,
+                                  void* stream);
+
+/* pipelines.registration.correspondences_from_features(source, target, mutual_filter, mutual_consistency_ratio)
+ * ("features").  src, tgt: device float64, point-major (one row of dim values per feature column of
+ * Open3D's Feature.data).  The match of source row i is the target row with the smallest (d2, index), d2 the
+ * sequential sum over j = 0 .. dim-1 of (s_j - t_j) (s_j - t_j).  Without mutual_filter corr_out (device int32
+ * [n][2]) receives (i, match(i)) for every i.  With it the targets are matched against the source the same way and
+ * only the pairs with match_t(match(i)) == i are kept, in i order; if fewer than
+ * mutual_consistency_ratio * (double)n are kept, all n pairs are returned instead and *fell_back_host (nullable) is
+ * set to 1 (0 otherwise).  dim must lie in 1..128; n == 0 gives zero pairs; m == 0 with n > 0 is refused. */
+ot_status ot_correspondences_from_features(const double* src /* n x dim */, int64_t n, const double* tgt /* m x dim */,
+                                           int64_t m, int32_t dim, int32_t mutual_filter, double mutual_consistency_ratio,
+                                           int32_t* corr_out /* n x 2 */, int64_t* n_corr_host, int32_t* fell_back_host,
+                                           void* stream);
+
 /* The configs[2] filter chain for a batch of frames, device-resident end to end (not an Open3D API: the batch form
  * of the per-frame calls below, results bit-identical to them).  Per frame f of a run:
  *   create_from_color_and_depth(depth_scale, depth_trunc) -> PointCloud.create_from_rgbd_image(intrinsic,

@@ -66,6 +66,8 @@ SIGNATURES = {
     "ot_evaluate_registration": [_p, _i64, _p, _i64, _d, _p, _pd, _pd, _p, _pi64, _p],
     "ot_registration_icp": [_p, _i64, _p, _i64, _d, _p, _d, _d, _i32, _p, _pd, _pd, _p, _pi64, C.POINTER(C.c_int32),
                             _p],
+    "ot_compute_fpfh_feature": [_p, _p, _i64, _i32, _d, _p, _p, _p],
+    "ot_correspondences_from_features": [_p, _i64, _p, _i64, _i32, _i32, _d, _p, _pi64, C.POINTER(C.c_int32), _p],
     "ot_filter_min_z": [_p, _p, _i64, _d, _p, _p, _pi64, _p],
     "ot_gather_rows3": [_p, _p, _i64, _p, _p],
     "ot_tsdf_create": [_d, _d, _i32, _i32, _i32, _i64, C.POINTER(_p)],

@@ -4,13 +4,9 @@
 // Neighbours come from the uniform cell grid of grid.h, sized as SOR sizes it (sor_cell_target).  The result is
 // defined by the distances and the point indices alone: the first k points in ascending (d2, index) order, so the
 // grid only decides which candidates a query scans.
-//   k_nrm_cov      : one lane per query in the grid's sorted cell order.  The lane keeps its (d2, index) list, sorted,
-//                    in LDS (entry p of lane l at [p * 64 + l]: conflict-free, no scratch whatever k is).  It scans
-//                    the 3x3x3 block of its cell (the precomputed column ranges), then Chebyshev rings of columns,
-//                    until the k-th entry is provably inside the scanned block (block_guard) or, hybrid search, the
-//                    block provably covers the radius; after NRM_RMAX rings, or once every point was scanned, the
-//                    search ends on its own: the lane scans the whole cloud (isolated points only).  The neighbours
-//                    are then gathered in list order for the nine sequential sums (the order is the result).
+//   k_nrm_cov      : one lane per query in the grid's sorted cell order.  The lane finds its sorted (d2, index) list
+//                    in LDS (nb_list.h: the search, shared with features.hip), then gathers the neighbours in list
+//                    order for the nine sequential sums (the order is the result).
 //   k_nrm_from_cov : one lane per point: Open3D's FastEigen3x3 on the covariance, the zero-normal and prior rules.
 //   k_nrm_orient / k_nrm_normalize : elementwise.
 // Everything is float64 without contraction; acos and cos (device library) are the only operations whose last bits
@@ -18,51 +14,10 @@
 #include <algorithm>
 #include <cmath>
 
+#include "nb_list.h"
 #include "sor.h"
 
 namespace ot {
-
-constexpr int NRM_RMAX = 6;  // rings walked per lane before the whole-cloud scan (speed only, never a result)
-
-// the 3x3 columns of a cell's block, nearest first (t = (dx + 1) * 3 + dy + 1): the k-th distance tightens early, so
-// fewer later candidates enter the list only to be pushed out again (the order never changes the list)
-__constant__ unsigned char c_nrm_cols3[NBR3] = {4, 1, 3, 5, 7, 0, 2, 6, 8};
-
-// (d, id) sorts before (e, ie)
-__device__ inline bool nb_less(double d, unsigned id, double e, unsigned ie) { return d < e || (d == e && id < ie); }
-
-// The lane's list Ld / Li (already offset by the lane; stride 64) holds cnt <= kk entries ascending by (d2, index);
-// insert (d, id), dropping the last entry of a full list.
-__device__ inline void nb_insert(double* Ld, unsigned* Li, int& cnt, int kk, double d, unsigned id) {
-    int p;
-    if (cnt < kk) {
-        p = cnt++;
-    } else {
-        p = kk - 1;
-        if (!nb_less(d, id, Ld[p * 64], Li[p * 64])) return;
-    }
-    while (p > 0) {
-        const double dp = Ld[(p - 1) * 64];
-        const unsigned ip = Li[(p - 1) * 64];
-        if (!nb_less(d, id, dp, ip)) break;
-        Ld[p * 64] = dp;
-        Li[p * 64] = ip;
-        --p;
-    }
-    Ld[p * 64] = d;
-    Li[p * 64] = id;
-}
-
-// candidates [beg, end) of the sorted points; kth: the last entry's d2 once the list is full, +inf before
-__device__ inline void nb_scan(const GridDev& g, const double q[3], int beg, int end, double* Ld, unsigned* Li,
-                               int& cnt, int kk, double& kth) {
-    for (int m = beg; m < end; ++m) {
-        const double d = d2_l2(q, g.sxyz + (int64_t)m * 3);
-        if (d > kth) continue;
-        nb_insert(Ld, Li, cnt, kk, d, g.sidx[m]);
-        if (cnt == kk) kth = Ld[(kk - 1) * 64];
-    }
-}
 
 // r2 <= 0: KNN; r2 > 0: hybrid (the first kk, of these the ones with d2 < r2)
 template <int KMAX>
@@ -75,55 +30,7 @@ __global__ __launch_bounds__(64) void k_nrm_cov(GridDev g, const double* __restr
     double* Ld = s_d + threadIdx.x;
     unsigned* Li = s_i + threadIdx.x;
     const int kk = (int)((int64_t)k < n ? k : n);  // <= KMAX (host)
-    const double q[3] = {g.sxyz[j * 3], g.sxyz[j * 3 + 1], g.sxyz[j * 3 + 2]};
-    int cc[3];
-    query_cell(g, j, cc[0], cc[1], cc[2]);
-    int cnt = 0;
-    double kth = INFINITY;
-    long long have = 0;  // points scanned: every cell of the block exactly once
-    const int2* r3 = g.nbr3 + (int64_t)g.pcell[j] * NBR3;
-    for (int u = 0; u < NBR3; ++u) {
-        const int2 se = r3[c_nrm_cols3[u]];
-        nb_scan(g, q, se.x, se.y, Ld, Li, cnt, kk, kth);
-        have += se.y - se.x;
-    }
-    for (int r = 1; have < n; ++r) {
-        // every point outside the (2r+1)^3 block is farther than guard (margins: block_guard), so it sorts after
-        // the k-th entry, or lies outside the radius
-        const double guard = block_guard(g, q, g.origin, cc, (double)r);
-        if (guard > 0.0) {
-            const double g2 = guard * guard;
-            if (kth < g2 || (r2 > 0.0 && g2 >= r2)) break;
-        }
-        if (r >= NRM_RMAX) {  // an isolated query: the whole cloud from scratch
-            cnt = 0;
-            kth = INFINITY;
-            nb_scan(g, q, 0, (int)n, Ld, Li, cnt, kk, kth);
-            break;
-        }
-        const int R = r + 1;  // ring R: border columns over z-R .. z+R, inner columns their two end cells
-        for (int dx = -R; dx <= R; ++dx)
-            for (int dy = -R; dy <= R; ++dy) {
-                const int2 col = grid_column(g, 0, cc[0] + dx, cc[1] + dy);
-                if (col.y == 0) continue;
-                if (dx == -R || dx == R || dy == -R || dy == R) {
-                    const int2 se = column_range(g, col, cc[2] - R, cc[2] + R);
-                    nb_scan(g, q, se.x, se.y, Ld, Li, cnt, kk, kth);
-                    have += se.y - se.x;
-                } else {
-                    const int2 a = column_range(g, col, cc[2] - R, cc[2] - R);
-                    const int2 b = column_range(g, col, cc[2] + R, cc[2] + R);
-                    nb_scan(g, q, a.x, a.y, Ld, Li, cnt, kk, kth);
-                    nb_scan(g, q, b.x, b.y, Ld, Li, cnt, kk, kth);
-                    have += (a.y - a.x) + (b.y - b.x);
-                }
-            }
-    }
-    int m = cnt;
-    if (r2 > 0.0) {
-        m = 0;
-        while (m < cnt && Ld[m * 64] < r2) ++m;
-    }
+    const int m = nb_search(g, n, j, kk, r2, Ld, Li);
     double* C = cov + (int64_t)g.sidx[j] * 9;
     if (m < 3) {
         C[0] = 1.0, C[1] = 0.0, C[2] = 0.0;

@@ -93,6 +93,11 @@ enum class Slot : int {
     MF_COMPACT,          // block counts of its compactions (consumed inside compact())
     MF_BOUNDS_PARTIALS,  // clustering: bounds partials
     MF_PING,             // filters: the second buffer of the ping-pong
+    // features.hip
+    FEAT_LISTS,    // FPFH: per point the neighbour list (length, indices, d2), read by the SPFH and the FPFH kernel
+    FEAT_SPFH,     // FPFH: the SPFH rows when the caller does not ask for them
+    FEAT_MATCH,    // matching: the per-split (d2, index) minima and the two match tables
+    FEAT_COMPACT,  // matching: block counts of the mutual filter's compaction (consumed inside compact())
     COUNT
 };
 

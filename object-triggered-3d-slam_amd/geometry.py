@@ -244,12 +244,12 @@ class KDTreeSearchParamHybrid(KDTreeSearchParam):
         return f"KDTreeSearchParamHybrid with radius = {self.radius:f} and max_nn = {self.max_nn}"
 
 
-def _search_args(who, search_param):
+def _search_args(who, search_param, limit=64, what="the covariance is a distance-ordered sum"):
     """(knn, radius) of the C ABI (radius 0.0: pure KNN), the refusals of DESIGN.md §4 "normals" raised here,
-    before any device work."""
+    before any device work.  limit: the longest neighbour list the caller's kernels keep (64: normals, 128: FPFH)."""
     if isinstance(search_param, KDTreeSearchParamRadius):
         raise RuntimeError(f"[{who}] KDTreeSearchParamRadius is not supported: its neighbour list is unbounded and "
-                           "the covariance is a distance-ordered sum over at most 64 neighbours; use "
+                           f"{what} over at most {limit} neighbours; use "
                            "KDTreeSearchParamHybrid(radius, max_nn)")
     if isinstance(search_param, KDTreeSearchParamHybrid):
         knn, radius, name = search_param.max_nn, search_param.radius, "max_nn"
@@ -260,8 +260,8 @@ def _search_args(who, search_param):
     else:
         raise RuntimeError(f"[{who}] search_param must be KDTreeSearchParamKNN or KDTreeSearchParamHybrid, got "
                            f"{type(search_param).__name__}")
-    if not 1 <= knn <= 64:
-        raise RuntimeError(f"[{who}] {name} must lie in 1..64 (the neighbour list is kept on chip), got {knn}")
+    if not 1 <= knn <= limit:
+        raise RuntimeError(f"[{who}] {name} must lie in 1..{limit} (the neighbour list is kept on chip), got {knn}")
     return int(knn), float(radius)
 
 
