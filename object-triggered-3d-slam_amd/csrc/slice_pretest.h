@@ -1,5 +1,5 @@
 // slice_pretest.h — "no voxel of this slice can be a candidate in this frame", decided from the slice's bounding box in
-// the image and a tile-max depth map, before the integrate's frame loop (tsdf.hip integrate_body).  One text for the
+// the image and a tile-max depth map, before the integrate's frame loop (tsdf_integrate.h integrate_body).  One text for the
 // device prologue and for the host program that checks it against brute force (tests/test_slice_pretest_bound.py).
 //
 // A coarse slice is 8 x 8 x 4 voxels of a unit (slice s: x in [4 (s & 2), +8), y in [8 (s & 1), +8), z in

@@ -249,9 +249,15 @@ struct BatchTouchParams {
     unsigned* tmax;     // the set's tile-max depth maps, written by the staging (frame f's at tmax + f * tiles); nullptr: none
     int H;
     int onepass;        // eligible frames are staged in 8 x 8 tile order and their map words reduced from the depths in
-                        // registers (tsdf.hip stage_tile_quads); 0: every frame by pixel chunks, the map from a second read
+                        // registers (tsdf_stage.h stage_tile_quads); 0: every frame by pixel chunks, the map from a second read
 };
 
+// The split front end's staging tile and the layout of its tile masks (k_stage_mask, k_stage_tiles: tsdf_frontend.hip;
+// the host sizes the masks and refuses frames they do not fit: tsdf.hip tmask_fits)
+constexpr int STX = 32, STY = 16;  // staging tile: 32 pixels (one 8-lane group of quads per row) x 16 rows
+constexpr int SM_WORDS = 2048;  // LDS map words: tile rows * words per row (8 KiB; 16K x 16K-pixel frames)
+constexpr int SM_PARTS = 4;     // mask workgroups (and maps) per frame
+constexpr int ST_MAX_TILES_X = 256;
 // parameters of the split front end's tile-mask kernel (tsdf.hip make_stage_params)
 struct StageMaskParams {
     int W, H, tiles_x, tiles_y, wpr;  // wpr: 32-bit mask words per tile row
@@ -266,6 +272,21 @@ struct UnitWork {
     int kx, ky, kz;           // unit key
     unsigned long long mask;   // frames of the batch that touch the unit (bit f = frame f), frames 0..63
     unsigned long long mask1;  // frames 64..127 (bit f - 64); 0 in a batch of at most 64 frames
+};
+// a sharded volume's work list: units seen by this many of the batch's frames or more are listed from the front, the
+// rest from the back (k_batch_units writes it so, the fused launches' integrate_body reads it so)
+constexpr int WORK_HEAVY_FRAMES = 32;
+
+// The form of a batch's integrate: which instantiation of k_batch_integrate / k_integrate_touch runs it.
+struct IntegrateForm {
+    bool c64 = false;   // colour state in float64 (the volume's colour precision)
+    bool fast = false;  // quotients from the reciprocal table (tsdf_integrate.h RCP_N) instead of IEEE divisions
+    bool fine = false;  // fine slices: 2 voxels per lane along z, 32 waves per unit instead of 16 -- for batches with
+                        // few units (tsdf.hip slice_form)
+    int kt = 1;         // a fine form's frame pipeline depth KT, 1..3 (integrate_item's ZB == 2 loop); 1 when coarse
+    // dense index over the forms, below N_INDEX (the occupancy cache)
+    static constexpr int N_INDEX = 32;
+    int index() const { return (c64 ? 2 : 0) + (fast ? 1 : 0) + (fine ? 4 + ((kt - 1) << 3) : 0); }
 };
 
 // How a batch runs (tsdf.hip plan_batch chooses once per batch; everything after it reads the plan):
@@ -290,7 +311,8 @@ struct BatchCtx {
     IntegrateParams ip0;
     StageMaskParams sq{};       // split: a replay stages its units' tiles too (units the full hash dropped were in no
     unsigned* smask = nullptr;  // work list of the first pass, so their footprints were never staged); the tile masks
-    int n, pc, variant;
+    int n, pc;
+    IntegrateForm form;
 };
 
 struct PendingFrame {
@@ -450,8 +472,31 @@ struct TsdfHooks {
 };
 extern TsdfHooks g_tsdf_hooks;
 
-// the three TSDF translation units share these: tsdf.hip (integrate: kernels and the batch pipeline), tsdf_exchange.hip
-// (unit order, export, import, border halo), tsdf_volume.hip (create, reset, settings, read-outs, hooks)
+// The launchers of the integrate pipeline's kernels: the only way from the host batch pipeline (tsdf.hip) to a kernel.
+// Each translation unit below holds its kernels and chooses between their forms; no other file names them.
+// tsdf_frontend.hip -- n: the batch's frames (more than WORD_FRAMES: the two-word forms)
+void launch_copy_frames(const BatchFrame* host, BatchFrame* dev, int n, hipStream_t stream);
+// replay: from the staged depths, no staging; split: the split front end's touch (k_batch_touch_split)
+void launch_touch(const BatchFrame* frames, const BatchTouchParams& tp, const TsdfDev& dev, int n, bool replay,
+                  bool split, hipStream_t stream);
+// missing_only: a replay that lists only the units without an id (k_batch_units<true, ..>)
+void launch_units(const TsdfDev& dev, UnitWork* work, int pc, unsigned* early_mail, int* wcount, unsigned seq, int n,
+                  bool missing_only, hipStream_t stream);
+void launch_stage_mask(const BatchFrame* frames, const StageMaskParams& q, const UnitWork* work, const int* wcount,
+                       unsigned* smask, hipStream_t stream);
+void launch_stage_tiles(const BatchFrame* frames, const StageMaskParams& q, const unsigned* smask, hipStream_t stream);
+// tsdf_integrate.hip, tsdf_integrate_wide.hip -- the k_batch_integrate of a form with `wg` waves per workgroup (coarse:
+// 1, 2 or 4; fine: INT_WG) reading one mask word / FMASK_WORDS, as hipLaunchKernel and the occupancy query take it
+const void* integrate_kernel_word(IntegrateForm form, int wg);
+const void* integrate_kernel_wide(IntegrateForm form, int wg);
+// tsdf_fused.hip -- k_integrate_touch / k_integrate_touch_fine: `nint` integrate workgroups over the deferred batch, then
+// the touch tiles of the next batch's `tn` frames
+hipError_t launch_integrate_touch(IntegrateForm form, const BatchFrame* frames, const IntegrateParams& p,
+                                  const TsdfDev& dev, const UnitWork* work, const int* wcount, int nint,
+                                  const BatchFrame* tframes, const BatchTouchParams& tp, int tn, hipStream_t stream);
+
+// shared by tsdf.hip (the batch pipeline), tsdf_exchange.hip (unit order, export, import, border halo) and
+// tsdf_volume.hip (create, reset, settings, read-outs, hooks):
 // room for `extra` more units before a kernel that allocates up to that many (imports): the pool grows now if needed
 ot_status reserve_units(ot_tsdf* vol, int64_t extra, hipStream_t stream);
 // the units an export lists: every unit in key order or, for a sharded volume, its own

@@ -1,5 +1,5 @@
 // tsdf_exchange.hip — units in and out of a ScalableTSDFVolume: the sorted unit order, export and import of whole units,
-// and the border halo a spatially sharded volume sends its neighbours (layout: tsdf.h; the integrate: tsdf.hip).
+// and the border halo a spatially sharded volume sends its neighbours (layout: tsdf.h; the integrate: tsdf.hip and the kernel files it launches).
 #include <algorithm>
 #include <cstring>
 

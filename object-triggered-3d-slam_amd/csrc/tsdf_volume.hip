@@ -1,6 +1,6 @@
 // tsdf_volume.hip — a ScalableTSDFVolume's life cycle and everything around the integrate: create, destroy, reset,
 // settings, counters, statistics, the profiling read-out, the shard setters, the pinned mailbox and the test hooks
-// (layout: tsdf.h; the integrate: tsdf.hip; the unit exchange: tsdf_exchange.hip).
+// (layout: tsdf.h; the integrate: tsdf.hip and the kernel files it launches; the unit exchange: tsdf_exchange.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -418,7 +418,7 @@ ot_status otx_touch_stage_blocks(int32_t blocks) {
 }
 
 // test hook: frames per touch workgroup (1..64, default TF): A/B timing and the parity of other groupings.  A group never
-// crosses a mask word (tsdf.hip touch_group_frames), whatever the count
+// crosses a mask word (tsdf_touch.h touch_group_frames), whatever the count
 ot_status otx_touch_frames(int32_t tf) {
     if (tf < 1 || tf > WORD_FRAMES) return fail(OT_ERR_INVALID_ARGUMENT, "otx_touch_frames: 1..64");
     g_tsdf_hooks.touch_tf = tf;

@@ -20,7 +20,7 @@ INTR = (64, 48, 56.0, 56.0, 31.5, 23.5)
 W, H = INTR[:2]
 VOXEL, TRUNC = 0.02, 0.04
 UNIT = 16 * VOXEL
-RCP_N = 2048                      # csrc/tsdf.hip: the table integrate serves frames since reset + the batch < RCP_N
+RCP_N = 2048                      # csrc/tsdf_integrate.h: the table integrate serves frames since reset + the batch < RCP_N
 WG_FORMS = (1, 2, 4)
 PRECISIONS = (64, 32)
 SITE_MM = 1120                    # depth of a site: z = 1.12 m, the middle of the units kz = 3

@@ -1,4 +1,4 @@
-"""The batch staging's one-pass form (csrc/tsdf.hip stage_tile_quads, otx_stage_onepass): an eligible frame (u16 depth,
+"""The batch staging's one-pass form (csrc/tsdf_stage.h stage_tile_quads, otx_stage_onepass): an eligible frame (u16 depth,
 16-B aligned, W % 8 == 0, colour absent or 4-B aligned) of a batch with tile-max maps is staged in 8 x 8 tile order and
 its map words are reduced from the converted depths the lanes hold; every other frame keeps the two-pass form.
 1. The staged records and map words, read back with otx_tsdf_staged, against a numpy model and between the two forms.

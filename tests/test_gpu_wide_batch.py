@@ -20,7 +20,7 @@ VOXEL, TRUNC = 0.02, 0.04
 WORD, CAP = 64, 128               # csrc/tsdf.h WORD_FRAMES, MAX_BATCH
 COUNTS = (1, 63, 64, 65, 66, 127, 128, 129, 130)
 HOOKS = ("otx_slice_pretest", "otx_integrate_workgroup", "otx_integrate_fine", "otx_integrate_depth")
-TOUCH_FRAMES = 2                  # csrc/tsdf.hip TF: otx_touch_frames has no "default" value to go back to
+TOUCH_FRAMES = 2                  # csrc/tsdf_touch.h TF: otx_touch_frames has no "default" value to go back to
 _cache = {}
 
 

@@ -1,4 +1,4 @@
-"""The reciprocal-table division of the FAST integrate kernels (csrc/tsdf.hip k_batch_integrate<C64, true>) is exact:
+"""The reciprocal-table division of the FAST integrate kernels (csrc/tsdf_integrate.h voxel_update<C64, true>) is exact:
 q0 = RN(a*y), q = fma(fma(-b, q0, a), y, q0) with y = RN(1/b) equals the IEEE quotient a/b for every integer
 divisor b in [1, 4096].  binary32 (tsdf mean): every 16th significand of a in [1, 2) against every b (the full
 exhaustive run, stride 1, is recorded in DESIGN.md); binary64 (colour mean): random and near-boundary a per b.

@@ -1,6 +1,7 @@
 // markstein_check.cpp — host proof-by-exhaustion / sampling for the reciprocal-table division of k_batch_integrate
-// (csrc/tsdf.hip, FAST kernels): q0 = RN(a*y), r = fma(-b, q0, a), q = fma(r, y, q0) with y = RN(1/b) must equal the
-// IEEE quotient RN(a/b) for every integer divisor b in [1, RCP_N] and every a the kernel can see.
+// (csrc/tsdf_integrate.h voxel_update, FAST kernels): q0 = RN(a*y), r = fma(-b, q0, a), q = fma(r, y, q0) with
+// y = RN(1/b) must equal the IEEE quotient RN(a/b) for every integer divisor b in [1, RCP_N] and every a the kernel can
+// see.
 //
 // binary32 (the tsdf mean): the result scales exactly with powers of two away from underflow, so checking every
 // significand of a in [1, 2) (both signs are symmetric) against every b is exhaustive.  `stride` > 1 checks every
